@@ -14,6 +14,11 @@ unix-socket RPC; rank 0 additionally runs the OpenAI-compatible gateway
 then K timed steps bracketed by gloo barrier + torch.cuda.synchronize on
 both sides; elapsed is the MAX over ranks; rank 0 prints ONE JSON line.
 
+A plain run does only that.  ``--dump-outputs DIR`` additionally writes
+the token ids every request of the last timed step received (prompts are
+seeded, so equal arguments give equal inputs); ``--full`` additionally
+reports per-rank engine statistics and admission events on stderr.
+
 Launch (driver):
   python bench.py --gpus 1 --steps K --warmup W
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
@@ -39,6 +44,7 @@ if REPO_ROOT not in sys.path:
 PROMPT_TOKENS = 128
 OUTPUT_TOKENS = 64
 CONCURRENCY_PER_GPU = 64
+STEP_ADMISSION_WINDOW_S = 0.25
 
 # distributed hardening (the first 8-GPU run happens
 # blind — a dead rank must produce a diagnosis, not a silent hang):
@@ -85,6 +91,10 @@ class LoopThread:
 
     def run(self, coro, timeout=None):
         return asyncio.run_coroutine_threadsafe(coro, self.loop).result(timeout)
+
+    def stop(self) -> None:
+        self.loop.call_soon_threadsafe(self.loop.stop)
+        self._thread.join(timeout=10)
 
 
 def start_worker(loopth: LoopThread, device: str, label: str, sock: str,
@@ -171,6 +181,59 @@ class LoadGen:
             self.proc.kill()
 
 
+class OutputRecorder:
+    """--dump-outputs: keeps, per request, the prompt ids the engine was
+    given and the token ids it handed back, by wrapping this rank's
+    engine.add_request / engine.step (two dict operations per call)."""
+
+    def __init__(self, engine) -> None:
+        self.records: dict = {}   # req_id -> (t_added, prompt_ids, token_ids)
+        add_request, step = engine.add_request, engine.step
+
+        def recording_add_request(req_id, prompt_ids, *a, **kw):
+            # registered BEFORE the engine sees the request: the engine
+            # thread may emit its first token right after add_request
+            self.records[req_id] = (time.monotonic(), list(prompt_ids), [])
+            try:
+                add_request(req_id, prompt_ids, *a, **kw)
+            except BaseException:
+                self.records.pop(req_id, None)
+                raise
+
+        def recording_step():
+            outs = step()
+            for o in outs:
+                rec = self.records.get(o.req_id)
+                if rec is not None:
+                    rec[2].append(o.token_id)
+            return outs
+
+        engine.add_request = recording_add_request
+        engine.step = recording_step
+
+    def since(self, t: float) -> list:
+        """(prompt_ids, token_ids) of every request added at or after
+        monotonic time ``t``."""
+        return [(p, list(toks)) for ta, p, toks in list(self.records.values())
+                if ta >= t]
+
+
+def write_outputs(out_dir: str, records: list, max_tokens: int) -> None:
+    """Rows are ordered by prompt, not by arrival, so two runs with the
+    same arguments line up row for row; short completions (EOS) are
+    padded with -1.  Token ids are exact in float32 (vocab < 2**24)."""
+    import numpy as np
+    records = sorted(records, key=lambda r: r[0])
+    width = max([max_tokens] + [len(toks) for _, toks in records])
+    token_ids = np.full((len(records), width), -1.0, dtype=np.float32)
+    for i, (_, toks) in enumerate(records):
+        token_ids[i, :len(toks)] = toks
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "token_ids.npy"), token_ids)
+    np.save(os.path.join(out_dir, "completion_tokens.npy"),
+            np.asarray([len(toks) for _, toks in records], dtype=np.float32))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -190,7 +253,17 @@ def main() -> None:
                          "headline metric stays bf16)")
     ap.add_argument("--device", default=None,
                     help="override torch device (tests: cpu)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the token ids every "
+                         "request of the LAST timed step received as "
+                         "DIR/token_ids.npy (+ DIR/completion_tokens.npy), "
+                         "rows ordered by prompt")
+    ap.add_argument("--full", action="store_true",
+                    help="also report what the headline figure does not "
+                         "need: per-rank engine statistics, admission "
+                         "events and (RLLI_STEP_TRACE=1) the step trace")
     args = ap.parse_args()
+    assert args.steps >= 1, "--steps must be at least 1"
     globals()["OUTPUT_TOKENS"] = args.output_tokens
 
     import torch
@@ -253,6 +326,19 @@ def main() -> None:
                           kv_dtype=args.kv_dtype, quant=args.quant)
     log(f"rank {rank}: worker up on {device} in {time.time() - t_init:.1f}s "
         f"({num_blocks} KV blocks)")
+    if not distributed:
+        # One worker, closed loop: every step delivers exactly
+        # --concurrency requests, and the engine admits the moment that
+        # many wait.  With the serving default (6 ms of quiet) a step was
+        # admitted as 1+63, 2+62 or 19+45 depending on arrival jitter,
+        # and since GEMM rounding depends on the batch shape the greedy
+        # tokens differed from run to run.  Holding admission until the
+        # step is complete makes what a step computes a function of its
+        # prompts alone; the window only bounds the wait if a client
+        # request goes missing.  (Several ranks share requests by random
+        # routing, a step is never "complete" there, so they keep 6 ms.)
+        worker.engine.admission_window_s = STEP_ADMISSION_WINDOW_S
+    recorder = OutputRecorder(worker.engine) if args.dump_outputs else None
     sync("post-worker-startup barrier")
 
     port = None
@@ -280,33 +366,54 @@ def main() -> None:
     sync("pre-timed barrier")
     t0 = time.monotonic()
     arm_watchdog("timed rounds", WATCHDOG_S)
+    t_last_step = t0
     for k in range(args.steps):
         if rank == 0:
+            if k == args.steps - 1:
+                t_last_step = time.monotonic()
             rounds_timed.append(loadgen.round())
     disarm_watchdog()
     sync("post-timed barrier")
     elapsed = time.monotonic() - t0
-    try:
-        h = loopth.run(worker.health(), timeout=30)
-        stats = h.get("engine_stats", {})
-        log(f"rank {rank} engine stats: {stats}")
-        admits = worker.engine.stats.get("admit_events", [])
-        log(f"rank {rank} admits (t, n, still_waiting): {admits[:40]}")
-        if worker.engine._trace:
-            tr = worker.engine._trace[-220:]
-            lines = []
-            prev = None
-            for t0, kind, ms in tr:
-                gap = 0.0 if prev is None else (t0 - prev) * 1e3
-                lines.append(f"{t0:.4f} +{gap:6.2f}ms {kind} host={ms}ms")
-                prev = t0
-            log("step trace (last 220):\n" + "\n".join(lines))
-    except Exception:
-        pass
+    if args.full:
+        try:
+            h = loopth.run(worker.health(), timeout=30)
+            stats = h.get("engine_stats", {})
+            log(f"rank {rank} engine stats: {stats}")
+            admits = worker.engine.stats.get("admit_events", [])
+            log(f"rank {rank} admits (t, n, still_waiting): {admits[:40]}")
+            if worker.engine._trace:
+                tr = worker.engine._trace[-220:]
+                lines = []
+                prev = None
+                for ts, kind, ms in tr:
+                    gap = 0.0 if prev is None else (ts - prev) * 1e3
+                    lines.append(f"{ts:.4f} +{gap:6.2f}ms {kind} host={ms}ms")
+                    prev = ts
+                log("step trace (last 220):\n" + "\n".join(lines))
+        except Exception:
+            pass
     if distributed:
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if recorder is not None:
+        # every request of the last timed step, whichever rank served it
+        # (CLOCK_MONOTONIC is shared by the ranks of one node)
+        if distributed:
+            holder = [t_last_step]
+            dist.broadcast_object_list(holder, src=0)
+            t_last_step = holder[0]
+        records = recorder.since(t_last_step)
+        if distributed:
+            gathered = [None] * world if rank == 0 else None
+            dist.gather_object(records, gathered, dst=0)
+            if rank == 0:
+                records = [r for part in gathered for r in part]
+        if rank == 0:
+            write_outputs(args.dump_outputs, records, args.output_tokens)
+            log(f"wrote {len(records)} completions to {args.dump_outputs}")
 
     if rank == 0:
         loadgen.close()
@@ -355,7 +462,24 @@ def main() -> None:
     if distributed:
         dist.barrier()
         dist.destroy_process_group()
-    os._exit(0)   # daemon loops/threads: exit hard once results are printed
+    # Orderly shutdown and a NORMAL interpreter exit: exit handlers (a
+    # profiler flushing its trace, coverage) never run under os._exit.
+    # The watchdog turns a wedged teardown into a stack dump + exit 1.
+    arm_watchdog("shutdown", 120)
+    for g in gateways:
+        try:
+            g.wait(timeout=10)
+        except Exception:
+            g.kill()
+    try:
+        loopth.run(worker.close(), timeout=30)
+    except Exception as e:                                # noqa: BLE001
+        log(f"worker close: {e!r}")
+    loopth.stop()
+    if on_gpu:
+        torch.cuda.synchronize()
+    sys.stdout.flush()
+    sys.stderr.flush()
 
 
 if __name__ == "__main__":

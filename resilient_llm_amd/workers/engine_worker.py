@@ -446,7 +446,12 @@ class EngineWorker(Worker):
                 e = self._adopted.pop(k, None)
                 if e:
                     self._adopted_by_rid.pop(e["rid"], None)
-            self._adopted[rid.rsplit("-", 1)[0]] = entry
+            # catch buffer only: the entry becomes ATTACHABLE (by gateway
+            # request_id, in _adopted) once the engine has really adopted
+            # the sequence.  A client whose source died mid-migration
+            # re-routes here at once; attaching it to an adoption that
+            # then fails (KV cache full) left it waiting forever on a
+            # sequence that never runs.
             self._adopted_by_rid[rid] = entry
         self.engine.queue_adopt(state)
         self._work_event.set()
@@ -458,11 +463,23 @@ class EngineWorker(Worker):
             await asyncio.sleep(0.02)
         if res is None or isinstance(res, Exception):
             with self._adopt_lock:
-                self._adopted.pop(rid.rsplit("-", 1)[0], None)
                 self._adopted_by_rid.pop(rid, None)
             if res is None:
                 raise WorkerError("adoption timed out")
             raise WorkerError(f"adoption failed: {res}")
+        key = rid.rsplit("-", 1)[0]
+        with self._adopt_lock:
+            restarted = any(r != rid and r.rsplit("-", 1)[0] == key
+                            for r in list(self._sinks))
+            if restarted:
+                self._adopted_by_rid.pop(rid, None)
+            else:
+                self._adopted[key] = entry
+        if restarted:
+            # the client did not wait for the adoption and is already
+            # regenerating here from its prompt: drop the adopted copy
+            # instead of running it headless
+            self._abort(rid)
 
     def _attach(self, req: GenerationRequest, mode: str):
         """Re-attach a client to an adopted request: returns the sink

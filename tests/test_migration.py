@@ -139,6 +139,58 @@ def test_worker_migrate_out_in_token_exact():
     asyncio.new_event_loop().run_until_complete(main())
 
 
+def test_early_reroute_survives_failed_adoption():
+    """The source dies mid-migration, so the client re-routes to the
+    target BEFORE the target's adoption has settled — and the adoption
+    then fails (KV cache full).  The re-routed generate() must not
+    attach to the doomed adoption (it would wait forever): it restarts
+    from the prompt and returns the full completion."""
+    import asyncio
+    import dataclasses as dc
+    from resilient_llm_amd.workers.base import (GenerationRequest,
+                                                WorkerError)
+    from resilient_llm_amd.workers.engine_worker import EngineWorker
+
+    async def main():
+        msgs = [{"role": "user", "content": "hello " * 30}]
+        req = GenerationRequest(request_id="mig-early", model="tiny",
+                                messages=msgs, max_tokens=120,
+                                temperature=0.0)
+        filler = GenerationRequest(request_id="filler", model="tiny",
+                                   messages=msgs, max_tokens=120,
+                                   temperature=0.0)
+        c = EngineWorker(device="cpu", model_name="tiny", num_blocks=64,
+                         max_batch_size=4)
+        want = await c.generate(dc.replace(req))
+        need = -(-(want.prompt_tokens + 120) // 16)
+
+        a = EngineWorker(device="cpu", model_name="tiny", num_blocks=64,
+                         max_batch_size=4)
+        # room for ONE such request: while the filler runs, adoption fails
+        b = EngineWorker(device="cpu", model_name="tiny",
+                         num_blocks=need + 2, max_batch_size=4)
+        src = asyncio.create_task(a.generate(dc.replace(req)))
+        fill = asyncio.create_task(b.generate(filler))
+        while not (a.engine.running and b.engine.running):
+            await asyncio.sleep(0.005)
+        blob = await a.migrate_out("mig-early")
+        mig = asyncio.create_task(b.migrate_in(blob))
+        while not b._adopted_by_rid and not mig.done():
+            await asyncio.sleep(0)
+        # the target now holds the (still unsettled) adoption: re-route
+        res = await asyncio.wait_for(b.generate(dc.replace(req)), timeout=60)
+        with pytest.raises(WorkerError):
+            await mig
+        assert res.completion_tokens == want.completion_tokens
+        assert res.text == want.text
+        assert (await fill).text == want.text
+        src.cancel()
+        for w in (a, b, c):
+            await w.close()
+
+    asyncio.new_event_loop().run_until_complete(main())
+
+
 # ---------------------------------------------------- gateway-level
 def test_gateway_admin_migrate_end_to_end():
     """Full stack: a long request is live-migrated between two worker
