@@ -91,11 +91,19 @@ class _Completions:
                temperature: float = 0.0, top_p: float = 1.0,
                stream: bool = False, timeout: Optional[float] = None,
                seed: Optional[int] = None,
+               logprobs: bool = False, top_logprobs: Optional[int] = None,
                extra_headers: Optional[dict] = None, **kw):
         payload = {"model": model, "messages": messages, "max_tokens": max_tokens,
                    "temperature": temperature, "top_p": top_p, "stream": stream}
         if seed is not None:
             payload["seed"] = seed
+        # OpenAI logprobs: the response's choices[0].logprobs.content then
+        # holds one {token, logprob, bytes, top_logprobs} entry per token
+        # (stream: per chunk); sent only when asked, like the SDK
+        if logprobs:
+            payload["logprobs"] = True
+        if top_logprobs is not None:
+            payload["top_logprobs"] = top_logprobs
         payload.update(kw)
         if stream:
             return self._client._post_stream("/chat/completions", payload,

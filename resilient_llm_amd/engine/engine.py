@@ -39,6 +39,12 @@ class SamplingParams:
     frequency_penalty: float = 0.0    # subtract per occurrence
     seed: Optional[int] = None
     stop_on_eos: bool = True
+    # OpenAI logprobs: report log p(token) of every emitted token, plus
+    # the top_logprobs (0..20) most likely alternatives.  The numbers are
+    # the MODEL's distribution (log-softmax of the raw logits): sampling
+    # temperature, top-p and penalties do not enter.
+    logprobs: bool = False
+    top_logprobs: int = 0
 
     @property
     def needs_torch_sampling(self) -> bool:
@@ -57,6 +63,8 @@ class StepOutput:
     finished: bool
     finish_reason: Optional[str] = None   # stop | length
     n_output_tokens: int = 0
+    logprob: Optional[float] = None        # set iff params.logprobs
+    top_logprobs: Optional[list] = None    # [(token_id, logprob), ...]
 
 
 @dataclasses.dataclass
@@ -65,6 +73,9 @@ class SeqState:
     prompt_ids: list
     params: SamplingParams
     output_ids: list = dataclasses.field(default_factory=list)
+    # one [logprob, [[token_id, logprob], ...]] record per output token
+    # when params.logprobs (plain lists/floats/ints: rides migration blobs)
+    output_logprobs: list = dataclasses.field(default_factory=list)
     blocks: list = dataclasses.field(default_factory=list)
     block_keys: Optional[list] = None      # prefix-cache content keys
     default_seed: int = 0                  # deterministic per arrival order
@@ -152,8 +163,10 @@ class LLMEngine:
         self._arrival_counter = 0
         self._batch_dirty = True
         self._graph_loaded = False
-        self._pending = None          # (seqs, event, host_tokens) 1-deep
+        # 1-deep: (seqs, event, host_tokens, host_logprobs | None)
+        self._pending = None
         self._pinned = None
+        self._pinned_lp = None        # allocated by the first logprobs step
         self.stats = {"prefill_steps": 0, "decode_steps": 0,
                       "prefill_time": 0.0, "decode_time": 0.0,
                       "prefill_tokens": 0, "decode_tokens": 0,
@@ -183,6 +196,9 @@ class LLMEngine:
     def add_request(self, req_id: str, prompt_ids: list,
                     params: Optional[SamplingParams] = None) -> None:
         params = params or SamplingParams()
+        if not 0 <= params.top_logprobs <= 20:
+            raise ValueError(
+                f"top_logprobs must be in 0..20, got {params.top_logprobs}")
         # out-of-vocab ids would fault the GPU inside the embedding
         # gather (hardware exception, not a python error) — reject at
         # the API boundary instead
@@ -276,17 +292,23 @@ class LLMEngine:
         return seq.blocks[pos // self.block_size] * self.block_size \
             + pos % self.block_size
 
-    def _finish(self, seq: SeqState, outs: list[StepOutput], token: int) -> bool:
+    def _finish(self, seq: SeqState, outs: list[StepOutput], token: int,
+                lp_record: Optional[list] = None) -> bool:
         p = seq.params
         reason = None
         if p.stop_on_eos and token in self.eos_ids:
             reason = "stop"
         elif len(seq.output_ids) >= p.max_tokens:
             reason = "length"
-        outs.append(StepOutput(req_id=seq.req_id, token_id=token,
-                               finished=reason is not None,
-                               finish_reason=reason,
-                               n_output_tokens=len(seq.output_ids)))
+        out = StepOutput(req_id=seq.req_id, token_id=token,
+                         finished=reason is not None,
+                         finish_reason=reason,
+                         n_output_tokens=len(seq.output_ids))
+        if lp_record is not None:
+            seq.output_logprobs.append(lp_record)
+            out.logprob = lp_record[0]
+            out.top_logprobs = [(t, v) for t, v in lp_record[1]]
+        outs.append(out)
         if reason is not None:
             self.kv.free(seq.blocks)
             seq.blocks = []
@@ -355,19 +377,20 @@ class LLMEngine:
     def _process_pending(self) -> list[StepOutput]:
         if self._pending is None:
             return []
-        seqs, event, buf = self._pending
+        seqs, event, buf, lp = self._pending
         self._pending = None
         if event is not None:
             event.synchronize()
         tokens = buf.tolist() if isinstance(buf, torch.Tensor) else buf
+        recs = self._lp_records(seqs, lp) if lp is not None else {}
         outs: list[StepOutput] = []
         still: list[SeqState] = []
         running_ids = {id(s) for s in self.running}
-        for seq, tok in zip(seqs, tokens):
+        for i, (seq, tok) in enumerate(zip(seqs, tokens)):
             if id(seq) not in running_ids:
                 continue               # aborted between forward and landing
             seq.output_ids.append(tok)
-            if not self._finish(seq, outs, tok):
+            if not self._finish(seq, outs, tok, recs.get(i)):
                 still.append(seq)
         if len(still) != len(seqs):
             self._batch_dirty = True
@@ -444,6 +467,7 @@ class LLMEngine:
                     state = {"rid": rid,
                              "prompt_ids": list(seq.prompt_ids),
                              "output_ids": [],
+                             "output_logprobs": [],
                              "params": dataclasses.asdict(seq.params),
                              "default_seed": seq.default_seed,
                              "n_cached": 0,
@@ -459,6 +483,7 @@ class LLMEngine:
                     state = {"rid": rid,
                              "prompt_ids": list(seq.prompt_ids),
                              "output_ids": list(seq.output_ids),
+                             "output_logprobs": list(seq.output_logprobs),
                              "params": dataclasses.asdict(seq.params),
                              "default_seed": seq.default_seed,
                              "n_cached": seq.n_cached,
@@ -478,6 +503,7 @@ class LLMEngine:
                     else:
                         state["n_cached"] = 0
                         state["output_ids"] = []
+                        state["output_logprobs"] = []
                     if seq.blocks:
                         self.kv.free(seq.blocks)
                         seq.blocks = []
@@ -524,6 +550,9 @@ class LLMEngine:
                                prompt_ids=list(state["prompt_ids"]),
                                params=params,
                                output_ids=list(state["output_ids"]),
+                               # absent in blobs from before logprobs
+                               output_logprobs=list(
+                                   state.get("output_logprobs") or []),
                                default_seed=state["default_seed"],
                                n_cached=int(state["n_cached"]))
                 kv_pair = state.get("kv")
@@ -551,6 +580,7 @@ class LLMEngine:
                 else:
                     seq.n_cached = 0
                     seq.output_ids = []
+                    seq.output_logprobs = []
                     if self.enable_prefix_caching:
                         seq.block_keys = block_hash_chain(
                             seq.prompt_ids, self.block_size)
@@ -626,6 +656,51 @@ class LLMEngine:
         gen = torch.Generator(device=row_logits.device)
         gen.manual_seed(self._seq_seed(s))
         return int(idx[int(torch.multinomial(sp, 1, generator=gen))])
+
+    def _lp_plan(self, seqs: list) -> Optional[tuple]:
+        """Which rows of a batch asked for logprobs: None — touching no
+        device state — when none did, else (row_indices, k, rows_dev)
+        with k the largest top_logprobs among them.  rows_dev is a
+        host->device upload, which synchronizes: call this only where
+        the host already waits (batch rebuild, mixed step), never per
+        decode step."""
+        idx = [i for i, s in enumerate(seqs) if s.params.logprobs]
+        if not idx:
+            return None
+        k = max(seqs[i].params.top_logprobs for i in idx)
+        return idx, k, torch.tensor(idx, dtype=torch.int32,
+                                    device=self.device)
+
+    def _compute_logprobs(self, logits: torch.Tensor, plan: tuple,
+                          tokens) -> tuple:
+        """One fused op over the step's logits for the plan's rows;
+        ``tokens`` are the step's FINAL per-row tokens (after any top-p /
+        penalty override), a list or an int32 device tensor.  Returns
+        (row_indices, chosen_lp, top_lp, top_ids) with the three results
+        still on the device; with device tokens nothing here waits for
+        the GPU."""
+        idx, k, rows = plan
+        if isinstance(tokens, torch.Tensor):
+            toks = tokens.index_select(0, rows)
+        else:
+            toks = torch.tensor([tokens[i] for i in idx], dtype=torch.int32,
+                                device=self.device)
+        return (idx,) + tuple(ops.token_logprobs(logits, rows, toks, k))
+
+    @staticmethod
+    def _lp_records(seqs: list, lp: tuple) -> dict:
+        """Host-side slicing of one step's logprob results: batch row ->
+        [logprob, [[token_id, logprob], ...]] with each request's own
+        top_logprobs count (the op ran at the step's maximum)."""
+        idx, chosen, top_lp, top_ids = lp
+        chosen, top_lp, top_ids = (chosen.tolist(), top_lp.tolist(),
+                                   top_ids.tolist())
+        recs = {}
+        for j, i in enumerate(idx):
+            n = seqs[i].params.top_logprobs
+            recs[i] = [chosen[j], [[top_ids[j][t], top_lp[j][t]]
+                                   for t in range(n)]]
+        return recs
 
     def _tune_budget(self, elapsed_s: float) -> None:
         """AIMD latency-targeted scheduling: multiplicative decrease of
@@ -736,6 +811,11 @@ class LLMEngine:
                       decode_seqs=()) -> tuple[int, list[StepOutput]]:
         t_s = time.monotonic()
         tokens = self._sample(logits, sampled_seqs)
+        plan = self._lp_plan(sampled_seqs)
+        recs = {}
+        if plan is not None:
+            recs = self._lp_records(
+                sampled_seqs, self._compute_logprobs(logits, plan, tokens))
         self.stats["prefill_sample_time"] += time.monotonic() - t_s
         n_chunk_tokens = 0
         for seq, start, n in chunk_plan:
@@ -744,7 +824,7 @@ class LLMEngine:
         outs: list[StepOutput] = []
         still_running: list[SeqState] = []
         decode_set = {id(s) for s in decode_seqs}
-        for seq, tok in zip(sampled_seqs, tokens):
+        for row, (seq, tok) in enumerate(zip(sampled_seqs, tokens)):
             if id(seq) in decode_set:
                 seq.n_cached += 1
             else:
@@ -756,7 +836,7 @@ class LLMEngine:
                                            // self.block_size]):
                         self.kv.register_block(seq.blocks[i], key)
             seq.output_ids.append(tok)
-            if not self._finish(seq, outs, tok):
+            if not self._finish(seq, outs, tok, recs.get(row)):
                 still_running.append(seq)
         self.running = [s for s in self.running
                         if id(s) not in decode_set] + still_running
@@ -768,8 +848,11 @@ class LLMEngine:
 
     # -------------------------------------- speculative decoding (lookup)
     def _spec_eligible(self) -> bool:
+        # verification rows have no per-token logprob plumbing: a batch
+        # with a logprobs request takes the normal decode step
         return self._pending is None and all(
             s.params.temperature == 0 and not s.params.needs_torch_sampling
+            and not s.params.logprobs
             for s in self.running)
 
     @staticmethod
@@ -891,6 +974,9 @@ class LLMEngine:
                                      dtype=torch.int64, device=dev)
         self._b_step_off = 0
         self._b_torch_sampling = any(s.params.needs_torch_sampling for s in seqs)
+        # requesting rows uploaded once per batch composition, so the
+        # decode steps add no host->device copy (= no synchronize)
+        self._b_lp_plan = self._lp_plan(seqs)
         self._batch_dirty = False
         self._graph_loaded = False
 
@@ -917,9 +1003,14 @@ class LLMEngine:
                 tok_dev = torch.tensor(tokens, dtype=torch.int32,
                                        device=self.device)
                 gr.override_tokens(tok_dev)
+            # eager, after the replay and on its logits buffer (stream-
+            # ordered before the next replay overwrites it), with the
+            # final tokens; never part of the captured body
+            lp = self._compute_logprobs(logits, self._b_lp_plan, tok_dev) \
+                if self._b_lp_plan is not None else None
             for seq in seqs:
                 seq.n_cached += 1      # KV of the fed token was appended
-            return self._queue_pending(seqs, tok_dev)
+            return self._queue_pending(seqs, tok_dev, lp)
         # eager path (no graphs, torch-side sampling, or out-of-envelope
         # block tables)
         pos = self._b_pos
@@ -938,6 +1029,8 @@ class LLMEngine:
             tok_dev = ops.sample(logits, self._b_temps, self._b_seeds,
                                  self._b_step_off)
             self._b_step_off += 1
+        lp = self._compute_logprobs(logits, self._b_lp_plan, tok_dev) \
+            if self._b_lp_plan is not None else None
         for seq in seqs:
             seq.n_cached += 1          # KV of the fed token was appended
         # advance device state in place: the NEXT forward feeds tok_dev
@@ -945,13 +1038,14 @@ class LLMEngine:
         # batch composition changes when the pending tokens land)
         self._b_ids.copy_(tok_dev)
         self._b_pos += 1
-        return self._queue_pending(seqs, tok_dev)
+        return self._queue_pending(seqs, tok_dev, lp)
 
-    def _queue_pending(self, seqs: list, tok_dev: torch.Tensor) \
-            -> list[StepOutput]:
-        """Hand the sampled tokens to the async landing pipeline: D2H
-        into the pinned ring, event-fenced; processed at the NEXT step
-        so steady decode never synchronizes."""
+    def _queue_pending(self, seqs: list, tok_dev: torch.Tensor,
+                       lp: Optional[tuple] = None) -> list[StepOutput]:
+        """Hand the sampled tokens (and, when a row asked, the step's
+        logprob results) to the async landing pipeline: D2H into the
+        pinned ring, ONE event fencing all copies; processed at the NEXT
+        step so steady decode never synchronizes."""
         B = len(seqs)
         if self.device.type == "cuda":
             if self._pinned is None or self._pinned.shape[0] < self.max_batch_size:
@@ -959,9 +1053,32 @@ class LLMEngine:
                                            dtype=torch.int32, pin_memory=True)
             host = self._pinned[:B]
             host.copy_(tok_dev, non_blocking=True)
+            if lp is not None:
+                lp = self._land_logprobs(lp)
             ev = torch.cuda.Event()
             ev.record()
-            self._pending = (list(seqs), ev, host)
+            self._pending = (list(seqs), ev, host, lp)
             return []
-        self._pending = (list(seqs), None, tok_dev.tolist())
+        self._pending = (list(seqs), None, tok_dev.tolist(), lp)
         return self._process_pending()
+
+    def _land_logprobs(self, lp: tuple) -> tuple:
+        """Queue the three logprob results' D2H copies into pinned
+        buffers (allocated on the first step that needs them; flat, so
+        every [R, k] view is contiguous)."""
+        idx, chosen, top_lp, top_ids = lp
+        if (self._pinned_lp is None
+                or self._pinned_lp[0].shape[0] < self.max_batch_size):
+            n = self.max_batch_size
+            self._pinned_lp = (
+                torch.empty(n, dtype=torch.float32, pin_memory=True),
+                torch.empty(n * 20, dtype=torch.float32, pin_memory=True),
+                torch.empty(n * 20, dtype=torch.int32, pin_memory=True))
+        R, k = top_lp.shape
+        h_chosen = self._pinned_lp[0][:R]
+        h_top_lp = self._pinned_lp[1][:R * k].view(R, k)
+        h_top_ids = self._pinned_lp[2][:R * k].view(R, k)
+        h_chosen.copy_(chosen, non_blocking=True)
+        h_top_lp.copy_(top_lp, non_blocking=True)
+        h_top_ids.copy_(top_ids, non_blocking=True)
+        return idx, h_chosen, h_top_lp, h_top_ids

@@ -363,6 +363,18 @@ class GatewayApp:
                 isinstance(stop, list)
                 and all(isinstance(s, str) for s in stop)):
             raise ValueError("'stop' must be a string or list of strings")
+        # OpenAI logprobs: a bool, plus top_logprobs 0..20 that is only
+        # meaningful with logprobs: true
+        lp = body.get("logprobs")
+        if lp is not None and not isinstance(lp, bool):
+            raise ValueError("'logprobs' must be a boolean")
+        tlp = body.get("top_logprobs")
+        if tlp is not None:
+            if (isinstance(tlp, bool) or not isinstance(tlp, int)
+                    or not 0 <= tlp <= 20):
+                raise ValueError("'top_logprobs' must be an integer in 0..20")
+            if not lp:
+                raise ValueError("'top_logprobs' requires 'logprobs': true")
         return body
 
     def _estimate(self, body: dict) -> tuple[int, int]:
@@ -391,6 +403,8 @@ class GatewayApp:
             stream=stream,
             consumer=consumer,
             stop=_normalize_stop(body.get("stop")),
+            logprobs=bool(body.get("logprobs")),
+            top_logprobs=int(body.get("top_logprobs") or 0),
         )
 
     def _record(self, ticket: Ticket, greq: Optional[GenerationRequest],
@@ -459,6 +473,12 @@ class GatewayApp:
                 prompt = prompt[0] if prompt else ""
             if not isinstance(prompt, str):
                 raise ValueError("'prompt' must be a string")
+            # legacy logprobs is a COUNT (0..5) of alternatives per token
+            n_lp = body.get("logprobs")
+            if n_lp is not None and (isinstance(n_lp, bool)
+                                     or not isinstance(n_lp, int)
+                                     or not 0 <= n_lp <= 5):
+                raise ValueError("'logprobs' must be an integer in 0..5")
         except (ValueError, json.JSONDecodeError) as e:
             return Response.error(400, str(e), err_type="invalid_request_error")
         if body.get("stream"):
@@ -467,6 +487,11 @@ class GatewayApp:
                 err_type="invalid_request_error")
         chat_body = dict(body)
         chat_body.pop("prompt", None)
+        chat_body.pop("logprobs", None)
+        chat_body.pop("top_logprobs", None)
+        if n_lp is not None:
+            chat_body["logprobs"] = True
+            chat_body["top_logprobs"] = n_lp
         chat_body["messages"] = [{"role": "user", "content": prompt}]
         chat_req = Request(req.method, req.path, req.headers,
                            json.dumps(chat_body).encode(), req.http_version)
@@ -475,12 +500,28 @@ class GatewayApp:
             return resp
         payload = json.loads(resp.body)
         text = payload["choices"][0]["message"]["content"]
+        legacy_lp = None
+        if n_lp is not None:
+            entries = (payload["choices"][0].get("logprobs")
+                       or {}).get("content") or []
+            offsets, pos = [], 0
+            for e in entries:
+                offsets.append(pos)
+                pos += len(e["token"])
+            legacy_lp = {
+                "tokens": [e["token"] for e in entries],
+                "token_logprobs": [e["logprob"] for e in entries],
+                "top_logprobs": [{t["token"]: t["logprob"]
+                                  for t in e["top_logprobs"]}
+                                 for e in entries],
+                "text_offset": offsets,
+            }
         out = {
             "id": payload["id"].replace("chatcmpl-", "cmpl-", 1),
             "object": "text_completion",
             "created": payload["created"],
             "model": payload["model"],
-            "choices": [{"index": 0, "text": text, "logprobs": None,
+            "choices": [{"index": 0, "text": text, "logprobs": legacy_lp,
                          "finish_reason": payload["choices"][0]["finish_reason"]}],
             "usage": payload["usage"],
         }
@@ -593,6 +634,9 @@ class GatewayApp:
                 "total_tokens": result.prompt_tokens + result.completion_tokens,
             },
         }
+        if greq.logprobs:      # absent (not null) when not requested
+            payload["choices"][0]["logprobs"] = {
+                "content": result.logprobs or []}
         headers = {
             "x-gateway-model-id": ticket.deployment.model_id,
             "x-gateway-device": worker.device,
@@ -687,6 +731,12 @@ class GatewayApp:
                                 "choices": [{"index": 0, "delta": delta,
                                              "finish_reason": chunk.finish_reason}],
                             }
+                            if greq.logprobs and chunk.logprob is not None:
+                                # replay-skipped chunks were dropped above
+                                # WITH their entries: each token's entry
+                                # reaches the client exactly once
+                                evt["choices"][0]["logprobs"] = {
+                                    "content": [chunk.logprob]}
                             yield f"data: {json.dumps(evt)}\n\n".encode()
                         sent_tokens += n_emitted
                         result = GenerationResult(

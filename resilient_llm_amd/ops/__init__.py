@@ -201,6 +201,19 @@ def sample(logits: torch.Tensor, temperatures: torch.Tensor,
     return ref.sample(logits, temperatures, seeds, step)
 
 
+def token_logprobs(logits: torch.Tensor, rows: torch.Tensor,
+                   tokens: torch.Tensor, k: int):
+    """Log-probability of ``tokens[i]`` under row ``rows[i]`` of the RAW
+    logits, plus each selected row's ``k`` (0..20) most likely tokens by
+    value descending, index ascending on ties -> (chosen_lp [R],
+    top_lp [R, k], top_ids [R, k]).  The numbers are the model's own
+    distribution: temperature, top-p and penalties do not enter."""
+    if logits.is_cuda:
+        _gpu()
+        return torch.ops.rlli.token_logprobs(logits, rows, tokens, k)
+    return ref.token_logprobs(logits, rows, tokens, k)
+
+
 def prefill_paged_attn(qkv, k_cache, v_cache, chunk_row0, chunk_pos0,
                        chunk_nrows, chunk_btrow, block_tables,
                        scale: float, n_q: int) -> torch.Tensor:

@@ -41,6 +41,7 @@ SOURCES = [
     "prefill_mfma.hip",
     "prefill_paged.hip",
     "sampling.hip",
+    "logprobs.hip",
     "skinny_gemm.hip",
     "skinny2.hip",
     "streamprobe.hip",

@@ -599,6 +599,48 @@ Tensor sample(const Tensor& logits, const Tensor& temperatures,
   return out;
 }
 
+// ------------------------------------------------------- token_logprobs
+// rows/tokens VALUES are trusted (as slot_mapping is): rows index
+// logits' first dim, tokens its second.
+std::tuple<Tensor, Tensor, Tensor> token_logprobs(const Tensor& logits,
+                                                  const Tensor& rows,
+                                                  const Tensor& tokens,
+                                                  int64_t k) {
+  check_bf16_contig(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(1) >= 1,
+              "logits must be [B, V] with V >= 1");
+  for (const Tensor* t : {&rows, &tokens}) {
+    TORCH_CHECK(t->scalar_type() == at::kInt && t->is_contiguous() &&
+                t->is_cuda() && t->device() == logits.device(),
+                "rows/tokens must be contiguous int32 on the logits' device");
+  }
+  TORCH_CHECK(tokens.numel() == rows.numel(), "rows/tokens length mismatch");
+  const int64_t vocab = logits.size(1);
+  TORCH_CHECK(vocab < (int64_t(1) << 30), "vocab too large");
+  TORCH_CHECK(k >= 0 && k <= 20 && k <= vocab,
+              "k must be in [0, min(20, vocab)], got ", k);
+  const int n_rows = int(rows.numel());
+  auto fopt = logits.options().dtype(at::kFloat);
+  Tensor chosen_lp = at::empty({n_rows}, fopt);
+  Tensor top_lp = at::empty({n_rows, k}, fopt);
+  Tensor top_ids = at::empty({n_rows, k}, logits.options().dtype(at::kInt));
+  if (n_rows == 0) return {chosen_lp, top_lp, top_ids};
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(logits.device());
+  const int n_split = rlli::logprobs_n_split(n_rows, int(vocab));
+  Tensor stats = at::empty({n_rows, n_split, 2}, fopt);
+  Tensor cand = at::empty({n_rows, n_split, k},
+                          logits.options().dtype(at::kLong));
+  rlli::launch_token_logprobs(
+      bf16_ptr(logits), rows.data_ptr<int32_t>(), tokens.data_ptr<int32_t>(),
+      chosen_lp.data_ptr<float>(), top_lp.data_ptr<float>(),
+      top_ids.data_ptr<int32_t>(), n_rows, int(vocab), int(k),
+      stats.data_ptr<float>(),
+      reinterpret_cast<uint64_t*>(cand.data_ptr<int64_t>()), n_split,
+      current_stream(logits));
+  check_launch("token_logprobs");
+  return {chosen_lp, top_lp, top_ids};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(rlli, m) {
@@ -626,6 +668,8 @@ TORCH_LIBRARY(rlli, m) {
   m.def("prefill_attn(Tensor q, Tensor k, Tensor v, Tensor cu_seqlens, "
         "float scale) -> Tensor");
   m.def("sample(Tensor logits, Tensor temperatures, Tensor seeds, int step) -> Tensor");
+  m.def("token_logprobs(Tensor logits, Tensor rows, Tensor tokens, int k) "
+        "-> (Tensor, Tensor, Tensor)");
   m.def("skinny_linear(Tensor x, Tensor w) -> Tensor");
   m.def("skinny2_linear(Tensor x, Tensor w, int splitk) -> Tensor");
   m.def("skinny2_silu_linear(Tensor gu, Tensor w, int splitk) -> Tensor");
@@ -651,6 +695,7 @@ TORCH_LIBRARY_IMPL(rlli, CUDA, m) {
   m.impl("prefill_attn_qkv", &prefill_attn_qkv);
   m.impl("prefill_attn", &prefill_attn);
   m.impl("sample", &sample);
+  m.impl("token_logprobs", &token_logprobs);
   m.impl("skinny_linear", &skinny_linear);
   m.impl("skinny2_linear", &skinny2_linear);
   m.impl("skinny2_silu_linear", &skinny2_silu_linear);

@@ -137,4 +137,21 @@ void launch_sample(
     uint64_t* partials, int n_split,   // [batch, n_split] workspace
     hipStream_t stream);
 
+// Fused log-softmax value of one emitted token per selected row plus the
+// row's k most likely tokens (value descending, index ascending on ties),
+// computed on the RAW logits — one pass over the selected rows, nothing
+// vocab-wide written (logprobs.hip).
+int logprobs_n_split(int rows, int vocab);   // phase-A split factor
+void launch_token_logprobs(
+    const uint16_t* logits,            // [batch, vocab] bf16
+    const int32_t* rows,               // [n_rows] row indices into logits
+    const int32_t* tokens,             // [n_rows] emitted token per row
+    float* chosen_lp,                  // [n_rows]
+    float* top_lp,                     // [n_rows, k]
+    int32_t* top_ids,                  // [n_rows, k]
+    int n_rows, int vocab, int k,
+    float* stats,                      // [n_rows, n_split, 2] workspace
+    uint64_t* cand,                    // [n_rows, n_split, k] workspace
+    int n_split, hipStream_t stream);
+
 }  // namespace rlli

@@ -169,6 +169,24 @@ def sample(logits: torch.Tensor, temperatures: torch.Tensor,
     return out
 
 
+def token_logprobs(logits: torch.Tensor, rows: torch.Tensor,
+                   tokens: torch.Tensor, k: int):
+    """Log-softmax (fp32, RAW logits — independent of temperature, top-p
+    and penalties) of ``tokens[i]`` in row ``rows[i]``, plus that row's
+    ``k`` most likely tokens ordered by value descending, index ascending
+    on ties.  Returns (chosen_lp [R] f32, top_lp [R, k] f32,
+    top_ids [R, k] int32)."""
+    if not 0 <= k <= min(20, logits.shape[1]):
+        raise ValueError(f"k must be in [0, min(20, vocab)], got {k}")
+    if rows.numel() != tokens.numel():
+        raise ValueError("rows/tokens length mismatch")
+    ridx = rows.long()
+    lp = torch.log_softmax(logits.index_select(0, ridx).float(), dim=-1)
+    chosen = lp.gather(1, tokens.long().unsqueeze(1)).squeeze(1)
+    vals, ids = torch.sort(lp, dim=-1, descending=True, stable=True)
+    return chosen, vals[:, :k].contiguous(), ids[:, :k].to(torch.int32)
+
+
 # ---- fp8-activation emitters (quantized-weight GEMM path) ----
 def quantize_fp8_rowwise(t: torch.Tensor):
     """Per-row fp8-e4m3 quantization: (q, scales) with q*scales ~= t."""

@@ -52,6 +52,8 @@ class GenerationRequest:
     stream: bool = False
     consumer: str = "anonymous"
     stop: Optional[list] = None      # OpenAI stop sequences (<= 4 strings)
+    logprobs: bool = False           # OpenAI logprobs / top_logprobs (0..20)
+    top_logprobs: int = 0
 
 
 @dataclasses.dataclass
@@ -60,6 +62,9 @@ class GenerationChunk:
     token_id: Optional[int] = None
     finish_reason: Optional[str] = None   # set on the last chunk
     prompt_tokens: Optional[int] = None   # set on the FIRST chunk
+    # this token's OpenAI logprobs entry when requested: {"token",
+    # "logprob", "bytes", "top_logprobs": [{"token", "logprob", "bytes"}]}
+    logprob: Optional[dict] = None
 
 
 @dataclasses.dataclass
@@ -69,6 +74,8 @@ class GenerationResult:
     completion_tokens: int
     finish_reason: str = "stop"
     ttft_ms: Optional[float] = None
+    # one OpenAI logprobs entry per completion token when requested
+    logprobs: Optional[list] = None
 
 
 class Worker:

@@ -290,7 +290,9 @@ class EngineWorker(Worker):
                                 top_p=req.top_p,
                                 presence_penalty=req.presence_penalty,
                                 frequency_penalty=req.frequency_penalty,
-                                seed=req.seed)
+                                seed=req.seed,
+                                logprobs=req.logprobs,
+                                top_logprobs=req.top_logprobs)
         self._req_counter += 1
         rid = f"{req.request_id}-{self._req_counter}"
         q: asyncio.Queue = asyncio.Queue()
@@ -319,6 +321,19 @@ class EngineWorker(Worker):
             raise WorkerThrottled(str(e)) from e
         self._work_event.set()
         return rid, q, len(prompt_ids)
+
+    # ------------------------------------------------------------ logprobs
+    def _lp_token(self, token_id: int, logprob: float) -> dict:
+        text = self.tokenizer.decode([token_id])
+        # JSON has no -inf: clamp like OpenAI does
+        return {"token": text, "logprob": max(float(logprob), -9999.0),
+                "bytes": list(text.encode("utf-8"))}
+
+    def _lp_entry(self, token_id: int, logprob: float, top) -> dict:
+        """One OpenAI ``logprobs.content`` entry for an emitted token."""
+        entry = self._lp_token(token_id, logprob)
+        entry["top_logprobs"] = [self._lp_token(t, v) for t, v in top]
+        return entry
 
     def _cleanup(self, rid: str) -> None:
         self._sinks.pop(rid, None)
@@ -433,6 +448,7 @@ class EngineWorker(Worker):
         # adopted sequence — outputs between adoption and registration
         # would otherwise drop on the floor (no sink, no entry)
         entry = {"rid": rid, "pre": list(state["output_ids"]),
+                 "pre_lp": list(state.get("output_logprobs") or []),
                  "prompt_len": len(state["prompt_ids"]),
                  "buf": [], "done": False, "t": time.monotonic()}
         with self._adopt_lock:
@@ -485,7 +501,9 @@ class EngineWorker(Worker):
         """Re-attach a client to an adopted request: returns the sink
         plus the tokens generated BEFORE attachment (migrated 'pre'
         tokens + anything buffered since adoption), or None when the
-        request_id is not adopted here."""
+        request_id is not adopted here.  The migrated tokens' saved
+        logprob records ride along so a re-attached client still gets
+        one entry per token."""
         with self._adopt_lock:
             entry = self._adopted.pop(req.request_id, None)
             if entry is None:
@@ -505,16 +523,16 @@ class EngineWorker(Worker):
             sink[3].extend(buffered)
             if buffered and buffered[-1].finished:
                 q.put_nowait((list(sink[3]), time.monotonic()))
-        return rid, q, entry["prompt_len"], pre
+        return rid, q, entry["prompt_len"], pre, list(entry.get("pre_lp") or [])
 
     async def generate(self, req: GenerationRequest) -> GenerationResult:
         t0 = time.monotonic()
         attached = self._attach(req, mode="final")
         if attached is not None:
-            rid, q, n_prompt, pre = attached
+            rid, q, n_prompt, pre, pre_lp = attached
         else:
             rid, q, n_prompt = self._enqueue(req, mode="final")
-            pre = []
+            pre, pre_lp = [], []
         self._in_flight += 1
         finished = False
         try:
@@ -534,12 +552,22 @@ class EngineWorker(Worker):
                 text = text[:cut]
                 finish = "stop"
             self.total_served += 1
+            entries = None
+            if req.logprobs:
+                # one entry per counted completion token: a stop-sequence
+                # cut shortens the text, not the token count or this list
+                entries = [self._lp_entry(t, r[0], r[1])
+                           for t, r in zip(pre, pre_lp)]
+                entries += [self._lp_entry(o.token_id, o.logprob,
+                                           o.top_logprobs)
+                            for o in outs if o.logprob is not None]
             return GenerationResult(
                 text=text,
                 prompt_tokens=n_prompt,
                 completion_tokens=len(token_ids),
                 finish_reason=finish,
-                ttft_ms=max(0.0, (first_t - t0) * 1000.0))
+                ttft_ms=max(0.0, (first_t - t0) * 1000.0),
+                logprobs=entries)
         finally:
             self._in_flight -= 1
             self._cleanup(rid)
@@ -549,10 +577,10 @@ class EngineWorker(Worker):
     async def _stream_impl(self, req: GenerationRequest) -> AsyncIterator[GenerationChunk]:
         attached = self._attach(req, mode="stream")
         if attached is not None:
-            rid, q, n_prompt, pre = attached
+            rid, q, n_prompt, pre, pre_lp = attached
         else:
             rid, q, n_prompt = self._enqueue(req)
-            pre = []
+            pre, pre_lp = [], []
         self._in_flight += 1
         finished = False
         # migrated 'pre' tokens replay as ONE CHUNK PER TOKEN so the
@@ -560,7 +588,11 @@ class EngineWorker(Worker):
         # tokens from index 0) stays in units with a fresh regeneration
         import types as _types
         pre_outs = [_types.SimpleNamespace(token_id=t, finished=False,
-                                           finish_reason=None) for t in pre]
+                                           finish_reason=None,
+                                           logprob=None, top_logprobs=None)
+                    for t in pre]
+        for o, rec in zip(pre_outs, pre_lp):
+            o.logprob, o.top_logprobs = rec[0], rec[1]
         pre_idx = 0
         try:
             emitted = ""
@@ -581,6 +613,10 @@ class EngineWorker(Worker):
                 if isinstance(out, Exception):
                     raise WorkerError(f"engine error: {out}") from out
                 token_ids.append(out.token_id)
+                lp_entry = None
+                if req.logprobs and out.logprob is not None:
+                    lp_entry = self._lp_entry(out.token_id, out.logprob,
+                                              out.top_logprobs)
                 full = self.tokenizer.decode_stream(token_ids, out.finished)
                 cut = _earliest_stop(full, stops)
                 if cut >= 0:
@@ -589,7 +625,8 @@ class EngineWorker(Worker):
                     yield GenerationChunk(text=delta, token_id=out.token_id,
                                           finish_reason="stop",
                                           prompt_tokens=n_prompt
-                                          if len(token_ids) == 1 else None)
+                                          if len(token_ids) == 1 else None,
+                                          logprob=lp_entry)
                     break
                 visible = len(full) if out.finished else max(
                     len(emitted), len(full) - hold)
@@ -598,7 +635,8 @@ class EngineWorker(Worker):
                 yield GenerationChunk(
                     text=delta, token_id=out.token_id,
                     finish_reason=out.finish_reason if out.finished else None,
-                    prompt_tokens=n_prompt if len(token_ids) == 1 else None)
+                    prompt_tokens=n_prompt if len(token_ids) == 1 else None,
+                    logprob=lp_entry)
                 if out.finished:
                     finished = True   # engine-side finish: no abort needed
                     break

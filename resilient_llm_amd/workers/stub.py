@@ -27,6 +27,23 @@ def estimate_tokens(text: str) -> int:
     return max(1, len(text) // 4)
 
 
+def synthetic_logprob_entry(text: str, index: int, top_n: int) -> dict:
+    """SYNTHETIC OpenAI logprobs entry for the stub's canned token
+    ``index``: there is no model behind the stub, so the numbers are made
+    up — deterministic, <= 0, descending over ``top_logprobs`` (whose
+    first element is the emitted token itself) — but the shape is exactly
+    what an engine worker returns, so gateway plumbing can be tested
+    without an engine."""
+    def tok(t: str, lp: float) -> dict:
+        return {"token": t, "logprob": lp, "bytes": list(t.encode("utf-8"))}
+
+    lp = -0.05 * (index % 7 + 1)
+    entry = tok(text, lp)
+    entry["top_logprobs"] = [tok(text if j == 0 else f"{text}~{j}",
+                                 lp - 0.5 * j) for j in range(top_n)]
+    return entry
+
+
 class StubWorker(Worker):
     def __init__(self, device_index: str, models: set[str],
                  token_delay_ms: float = 0.0, first_token_ms: float = 0.0,
@@ -88,6 +105,9 @@ class StubWorker(Worker):
                 completion_tokens=n,
                 finish_reason=finish,
                 ttft_ms=(time.monotonic() - t0) * 1000.0,
+                logprobs=[synthetic_logprob_entry(
+                    w if i == 0 else " " + w, i, req.top_logprobs)
+                    for i, w in enumerate(words)] if req.logprobs else None,
             )
         finally:
             self._in_flight -= 1
@@ -106,10 +126,13 @@ class StubWorker(Worker):
                 if self.token_delay_ms:
                     await asyncio.sleep(self.token_delay_ms / 1000.0)
                 last = i == n - 1
+                text = w if i == 0 else " " + w
                 yield GenerationChunk(
-                    text=(w if i == 0 else " " + w),
+                    text=text,
                     finish_reason=("length" if n == req.max_tokens else "stop") if last else None,
                     prompt_tokens=self._prompt_tokens(req) if i == 0 else None,
+                    logprob=synthetic_logprob_entry(text, i, req.top_logprobs)
+                    if req.logprobs else None,
                 )
             self.total_served += 1
         finally:
