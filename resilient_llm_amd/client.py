@@ -92,6 +92,8 @@ class _Completions:
                stream: bool = False, timeout: Optional[float] = None,
                seed: Optional[int] = None,
                logprobs: bool = False, top_logprobs: Optional[int] = None,
+               logit_bias: Optional[dict] = None,
+               top_k: Optional[int] = None, min_p: Optional[float] = None,
                extra_headers: Optional[dict] = None, **kw):
         payload = {"model": model, "messages": messages, "max_tokens": max_tokens,
                    "temperature": temperature, "top_p": top_p, "stream": stream}
@@ -104,6 +106,14 @@ class _Completions:
             payload["logprobs"] = True
         if top_logprobs is not None:
             payload["top_logprobs"] = top_logprobs
+        # logit_bias {token_id: bias in [-100, 100]} (ban / force tokens),
+        # top_k and min_p: each sent only when given
+        if logit_bias is not None:
+            payload["logit_bias"] = {str(k): v for k, v in logit_bias.items()}
+        if top_k is not None:
+            payload["top_k"] = top_k
+        if min_p is not None:
+            payload["min_p"] = min_p
         payload.update(kw)
         if stream:
             return self._client._post_stream("/chat/completions", payload,

@@ -45,6 +45,16 @@ class SamplingParams:
     # temperature, top-p and penalties do not enter.
     logprobs: bool = False
     top_logprobs: int = 0
+    # OpenAI logit_bias as [[token_id, bias], ...] ascending by id (plain
+    # lists: survives dataclasses.asdict, RPC frames, the TP broadcast and
+    # migration blobs, which a dict with int keys does not).  The bias is
+    # added to the logit before sampling; logprobs keep reporting the
+    # model's raw distribution.
+    logit_bias: Optional[list] = None
+    # keep the top_k most likely tokens (boundary ties stay); 0 = off
+    top_k: int = 0
+    # keep tokens with p >= min_p * p_max; 0 = off
+    min_p: float = 0.0
 
     @property
     def needs_torch_sampling(self) -> bool:
@@ -54,6 +64,16 @@ class SamplingParams:
         return ((self.temperature > 0 and self.top_p < 1.0)
                 or self.presence_penalty != 0.0
                 or self.frequency_penalty != 0.0)
+
+    @property
+    def needs_constrained_sampling(self) -> bool:
+        """Rows the fused constrained sampler serves on the device:
+        logit_bias, or top_k / min_p on a sampled row (both are no-ops
+        for greedy).  Static per request, so nothing about them crosses
+        the host per step.  A row that ALSO needs torch sampling stays
+        on the torch path, which applies the same constraints."""
+        return bool(self.logit_bias) or (
+            self.temperature > 0 and (self.top_k > 0 or self.min_p > 0))
 
 
 @dataclasses.dataclass
@@ -199,10 +219,31 @@ class LLMEngine:
         if not 0 <= params.top_logprobs <= 20:
             raise ValueError(
                 f"top_logprobs must be in 0..20, got {params.top_logprobs}")
+        if params.top_k < 0:
+            raise ValueError(f"top_k must be >= 0, got {params.top_k}")
+        if not 0.0 <= params.min_p <= 1.0:
+            raise ValueError(f"min_p must be in [0, 1], got {params.min_p}")
         # out-of-vocab ids would fault the GPU inside the embedding
         # gather (hardware exception, not a python error) — reject at
         # the API boundary instead
         vocab = getattr(self.model.config, "vocab_size", None)
+        if params.logit_bias:
+            bias = params.logit_bias
+            if len(bias) > 300:
+                raise ValueError(
+                    f"logit_bias holds at most 300 entries, got {len(bias)}")
+            ids = [int(t) for t, _ in bias]
+            if len(set(ids)) != len(ids):
+                raise ValueError("logit_bias token ids must be unique")
+            if min(ids) < 0 or (vocab and max(ids) >= vocab):
+                raise ValueError(
+                    f"logit_bias token id out of range [0, {vocab})")
+            if any(not abs(float(b)) <= 100 for _, b in bias):
+                raise ValueError("logit_bias values must be in [-100, 100]")
+            if ids != sorted(ids):      # the kernel searches an ascending list
+                params = dataclasses.replace(
+                    params, logit_bias=sorted([int(t), float(b)]
+                                              for t, b in bias))
         if vocab and prompt_ids:
             lo, hi = min(prompt_ids), max(prompt_ids)
             if lo < 0 or hi >= vocab:
@@ -621,6 +662,12 @@ class LLMEngine:
         seeds = torch.tensor([self._seq_seed(s) for s in seqs],
                              dtype=torch.int64, device=self.device)
         toks = ops.sample(logits, temps, seeds, 0)
+        # host path (first token, mixed step, batches with torch rows):
+        # the plan upload costs nothing next to the sync below
+        cs_plan = self._cs_plan(seqs)
+        if cs_plan is not None:
+            toks = self._apply_constrained(logits, cs_plan, temps, seeds, 0,
+                                           toks)
         special = [i for i, s in enumerate(seqs)
                    if s.params.needs_torch_sampling]
         if special:
@@ -628,6 +675,50 @@ class LLMEngine:
             for i in special:
                 toks[i] = self._sample_torch(logits[i], seqs[i])
         return toks.tolist()
+
+    def _cs_plan(self, seqs: list) -> Optional[tuple]:
+        """Which rows of a batch the constrained sampler serves: None —
+        touching no device state — when none does, else the device
+        tensors ops.sample_constrained takes (rows, top_k, min_p and the
+        CSR bias list) plus the rows as an index_copy_ index.  Host->
+        device uploads: call this only where the host already waits
+        (batch rebuild, mixed step), never per decode step.  Rows that
+        also need torch sampling are left to _sample_torch."""
+        idx = [i for i, s in enumerate(seqs)
+               if s.params.needs_constrained_sampling
+               and not s.params.needs_torch_sampling]
+        if not idx:
+            return None
+        offs, ids, vals = [0], [], []
+        for i in idx:
+            for t, b in seqs[i].params.logit_bias or ():
+                ids.append(int(t))
+                vals.append(float(b))
+            offs.append(len(ids))
+        dev = self.device
+
+        def i32(x):
+            return torch.tensor(x, dtype=torch.int32, device=dev)
+
+        def f32(x):
+            return torch.tensor(x, dtype=torch.float32, device=dev)
+
+        return (i32(idx), torch.tensor(idx, dtype=torch.long, device=dev),
+                i32([seqs[i].params.top_k for i in idx]),
+                f32([seqs[i].params.min_p for i in idx]),
+                i32(offs), i32(ids), f32(vals))
+
+    @staticmethod
+    def _apply_constrained(logits: torch.Tensor, plan: tuple,
+                           temps: torch.Tensor, seeds: torch.Tensor,
+                           step: int, toks: torch.Tensor) -> torch.Tensor:
+        """One fused op over the step's logits for the plan's rows; its
+        tokens replace those rows of ``toks`` (a copy — ``toks`` may be
+        the graph's output buffer).  Everything stays on the device."""
+        rows, rows_long, top_k, min_p, offs, ids, vals = plan
+        cs = ops.sample_constrained(logits, rows, temps, seeds, step, top_k,
+                                    min_p, offs, ids, vals)
+        return toks.index_copy(0, rows_long, cs)
 
     def _sample_torch(self, row_logits: torch.Tensor, s: SeqState) -> int:
         """Torch sampling path for rows the fused kernel cannot serve:
@@ -643,9 +734,23 @@ class LLMEngine:
                 counts[t] = counts.get(t, 0) + 1
             for t, c in counts.items():
                 lg[t] -= p.presence_penalty + p.frequency_penalty * c
+        if p.logit_bias:
+            lg = lg.clone()
+            lg[torch.tensor([int(t) for t, _ in p.logit_bias],
+                            device=lg.device)] += torch.tensor(
+                [float(b) for _, b in p.logit_bias], device=lg.device)
         if p.temperature <= 0:
             return int(lg.argmax())
         probs = torch.softmax(lg / p.temperature, -1)
+        if 0 < p.top_k < probs.shape[0] or p.min_p > 0:
+            # threshold masks on the probabilities (boundary ties stay),
+            # renormalised, ahead of the top-p cut
+            floor = p.min_p * probs.max()
+            if 0 < p.top_k < probs.shape[0]:
+                floor = torch.maximum(floor, probs.topk(p.top_k).values[-1])
+            probs = torch.where(probs >= floor, probs,
+                                torch.zeros_like(probs))
+            probs = probs / probs.sum()
         if p.top_p < 1.0:
             sp, idx = probs.sort(descending=True)
             keep = int((sp.cumsum(0) < p.top_p).sum()) + 1
@@ -853,6 +958,9 @@ class LLMEngine:
         return self._pending is None and all(
             s.params.temperature == 0 and not s.params.needs_torch_sampling
             and not s.params.logprobs
+            # verification takes the raw arg-max: a biased row cannot be
+            # verified that way (greedy top_k / min_p are no-ops and stay)
+            and not s.params.logit_bias
             for s in self.running)
 
     @staticmethod
@@ -977,6 +1085,8 @@ class LLMEngine:
         # requesting rows uploaded once per batch composition, so the
         # decode steps add no host->device copy (= no synchronize)
         self._b_lp_plan = self._lp_plan(seqs)
+        # likewise the constrained rows and their static constraints
+        self._b_cs_plan = self._cs_plan(seqs)
         self._batch_dirty = False
         self._graph_loaded = False
 
@@ -1003,6 +1113,16 @@ class LLMEngine:
                 tok_dev = torch.tensor(tokens, dtype=torch.int32,
                                        device=self.device)
                 gr.override_tokens(tok_dev)
+            elif self._b_cs_plan is not None:
+                # constrained rows: one device op on the captured logits,
+                # then the same post-replay correction — no host sync.
+                # The graph has already advanced its own seed buffer, so
+                # the op takes the rebuild-time seeds plus the steps since
+                tok_dev = self._apply_constrained(
+                    logits, self._b_cs_plan, self._b_temps, self._b_seeds,
+                    self._b_step_off, tok_dev)
+                gr.override_tokens(tok_dev)
+                self._b_step_off += 1
             # eager, after the replay and on its logits buffer (stream-
             # ordered before the next replay overwrites it), with the
             # final tokens; never part of the captured body
@@ -1028,6 +1148,10 @@ class LLMEngine:
         else:
             tok_dev = ops.sample(logits, self._b_temps, self._b_seeds,
                                  self._b_step_off)
+            if self._b_cs_plan is not None:
+                tok_dev = self._apply_constrained(
+                    logits, self._b_cs_plan, self._b_temps, self._b_seeds,
+                    self._b_step_off, tok_dev)
             self._b_step_off += 1
         lp = self._compute_logprobs(logits, self._b_lp_plan, tok_dev) \
             if self._b_lp_plan is not None else None

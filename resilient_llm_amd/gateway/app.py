@@ -375,6 +375,37 @@ class GatewayApp:
                 raise ValueError("'top_logprobs' must be an integer in 0..20")
             if not lp:
                 raise ValueError("'top_logprobs' requires 'logprobs': true")
+        # OpenAI logit_bias: {"<token id>": bias in [-100, 100]}, at most
+        # 300 entries; top_k / min_p as in vLLM/TGI (0 = off)
+        bias = body.get("logit_bias")
+        if bias is not None:
+            if not isinstance(bias, dict):
+                raise ValueError("'logit_bias' must be an object")
+            if len(bias) > 300:
+                raise ValueError("'logit_bias' holds at most 300 entries")
+            seen = set()
+            for key, val in bias.items():
+                if not (key.isascii() and key.isdigit()
+                        and int(key) < 2 ** 31):
+                    raise ValueError(
+                        f"'logit_bias' key {key!r} is not a token id")
+                if int(key) in seen:
+                    raise ValueError(
+                        f"'logit_bias' names token {int(key)} twice")
+                seen.add(int(key))
+                if (isinstance(val, bool) or not isinstance(val, (int, float))
+                        or not -100 <= val <= 100):
+                    raise ValueError(
+                        "'logit_bias' values must be numbers in [-100, 100]")
+        top_k = body.get("top_k")
+        if top_k is not None and (isinstance(top_k, bool)
+                                  or not isinstance(top_k, int) or top_k < 0):
+            raise ValueError("'top_k' must be an integer >= 0")
+        min_p = body.get("min_p")
+        if min_p is not None and (isinstance(min_p, bool)
+                                  or not isinstance(min_p, (int, float))
+                                  or not 0 <= min_p <= 1):
+            raise ValueError("'min_p' must be a number in [0, 1]")
         return body
 
     def _estimate(self, body: dict) -> tuple[int, int]:
@@ -405,6 +436,11 @@ class GatewayApp:
             stop=_normalize_stop(body.get("stop")),
             logprobs=bool(body.get("logprobs")),
             top_logprobs=int(body.get("top_logprobs") or 0),
+            logit_bias=sorted([int(k), float(v)] for k, v in
+                              body["logit_bias"].items())
+            if body.get("logit_bias") else None,
+            top_k=int(body.get("top_k") or 0),
+            min_p=float(body.get("min_p") or 0.0),
         )
 
     def _record(self, ticket: Ticket, greq: Optional[GenerationRequest],

@@ -201,6 +201,29 @@ def sample(logits: torch.Tensor, temperatures: torch.Tensor,
     return ref.sample(logits, temperatures, seeds, step)
 
 
+def sample_constrained(logits: torch.Tensor, rows: torch.Tensor,
+                       temperatures: torch.Tensor, seeds: torch.Tensor,
+                       step: int, top_k: torch.Tensor, min_p: torch.Tensor,
+                       bias_offsets: torch.Tensor, bias_ids: torch.Tensor,
+                       bias_vals: torch.Tensor) -> torch.Tensor:
+    """Sample rows ``rows`` of ``logits`` under logit_bias / top_k / min_p
+    -> int32 tokens [R].  With z = float(logit) + bias: keep z >= the
+    k-th largest z (boundary ties stay; k == 0 or k >= vocab is off) and
+    z >= z_max + T*ln(min_p) (0 is off), then ``sample``'s own greedy /
+    Gumbel-max choice over what is kept.  ``temperatures`` and ``seeds``
+    are per logits row (indexed by ``rows[r]``); ``top_k``, ``min_p`` and
+    the CSR bias list (``bias_ids`` ascending within a row) are per
+    selected row.  The logits are not modified."""
+    if logits.is_cuda:
+        _gpu()
+        return torch.ops.rlli.sample_constrained(
+            logits, rows, temperatures, seeds, step, top_k, min_p,
+            bias_offsets, bias_ids, bias_vals)
+    return ref.sample_constrained(logits, rows, temperatures, seeds, step,
+                                  top_k, min_p, bias_offsets, bias_ids,
+                                  bias_vals)
+
+
 def token_logprobs(logits: torch.Tensor, rows: torch.Tensor,
                    tokens: torch.Tensor, k: int):
     """Log-probability of ``tokens[i]`` under row ``rows[i]`` of the RAW

@@ -599,6 +599,62 @@ Tensor sample(const Tensor& logits, const Tensor& temperatures,
   return out;
 }
 
+// --------------------------------------------------- sample_constrained
+// rows / bias_offsets / bias_ids VALUES are trusted (as slot_mapping is);
+// the kernel still clamps the CSR slice and ignores ids outside the vocab.
+Tensor sample_constrained(const Tensor& logits, const Tensor& rows,
+                          const Tensor& temperatures, const Tensor& seeds,
+                          int64_t step, const Tensor& top_k,
+                          const Tensor& min_p, const Tensor& bias_offsets,
+                          const Tensor& bias_ids, const Tensor& bias_vals) {
+  check_bf16_contig(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(1) >= 1,
+              "logits must be [B, V] with V >= 1");
+  for (const Tensor* t : {&rows, &top_k, &bias_offsets, &bias_ids}) {
+    TORCH_CHECK(t->scalar_type() == at::kInt && t->is_contiguous() &&
+                t->is_cuda() && t->device() == logits.device(),
+                "rows/top_k/bias_offsets/bias_ids must be contiguous int32 "
+                "on the logits' device");
+  }
+  for (const Tensor* t : {&temperatures, &min_p, &bias_vals}) {
+    TORCH_CHECK(t->scalar_type() == at::kFloat && t->is_contiguous() &&
+                t->is_cuda() && t->device() == logits.device(),
+                "temperatures/min_p/bias_vals must be contiguous float32 "
+                "on the logits' device");
+  }
+  TORCH_CHECK(seeds.scalar_type() == at::kLong && seeds.is_contiguous() &&
+              seeds.is_cuda() && seeds.device() == logits.device(),
+              "seeds must be contiguous int64 on the logits' device");
+  const int64_t batch = logits.size(0);
+  const int64_t vocab = logits.size(1);
+  TORCH_CHECK(temperatures.numel() == batch && seeds.numel() == batch,
+              "temperatures/seeds must have one entry per logits row");
+  const int64_t n_rows = rows.numel();
+  TORCH_CHECK(top_k.numel() == n_rows && min_p.numel() == n_rows &&
+              bias_offsets.numel() == n_rows + 1,
+              "rows/top_k/min_p/bias_offsets length mismatch");
+  TORCH_CHECK(bias_ids.numel() == bias_vals.numel(),
+              "bias_ids/bias_vals length mismatch");
+  TORCH_CHECK(bias_ids.numel() < (int64_t(1) << 31), "bias list too long");
+  TORCH_CHECK(vocab <= rlli::sample_constrained_max_vocab(),
+              "sample_constrained supports vocab <= ",
+              rlli::sample_constrained_max_vocab(), ", got ", vocab);
+  Tensor out = at::empty({n_rows}, logits.options().dtype(at::kInt));
+  if (n_rows == 0) return out;
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(logits.device());
+  rlli::launch_sample_constrained(
+      bf16_ptr(logits), rows.data_ptr<int32_t>(),
+      temperatures.data_ptr<float>(),
+      reinterpret_cast<const uint64_t*>(seeds.data_ptr<int64_t>()),
+      uint64_t(step), top_k.data_ptr<int32_t>(), min_p.data_ptr<float>(),
+      bias_offsets.data_ptr<int32_t>(), bias_ids.data_ptr<int32_t>(),
+      bias_vals.data_ptr<float>(), int(bias_ids.numel()),
+      out.data_ptr<int32_t>(), int(n_rows), int(vocab),
+      current_stream(logits));
+  check_launch("sample_constrained");
+  return out;
+}
+
 // ------------------------------------------------------- token_logprobs
 // rows/tokens VALUES are trusted (as slot_mapping is): rows index
 // logits' first dim, tokens its second.
@@ -668,6 +724,9 @@ TORCH_LIBRARY(rlli, m) {
   m.def("prefill_attn(Tensor q, Tensor k, Tensor v, Tensor cu_seqlens, "
         "float scale) -> Tensor");
   m.def("sample(Tensor logits, Tensor temperatures, Tensor seeds, int step) -> Tensor");
+  m.def("sample_constrained(Tensor logits, Tensor rows, Tensor temperatures, "
+        "Tensor seeds, int step, Tensor top_k, Tensor min_p, "
+        "Tensor bias_offsets, Tensor bias_ids, Tensor bias_vals) -> Tensor");
   m.def("token_logprobs(Tensor logits, Tensor rows, Tensor tokens, int k) "
         "-> (Tensor, Tensor, Tensor)");
   m.def("skinny_linear(Tensor x, Tensor w) -> Tensor");
@@ -695,6 +754,7 @@ TORCH_LIBRARY_IMPL(rlli, CUDA, m) {
   m.impl("prefill_attn_qkv", &prefill_attn_qkv);
   m.impl("prefill_attn", &prefill_attn);
   m.impl("sample", &sample);
+  m.impl("sample_constrained", &sample_constrained);
   m.impl("token_logprobs", &token_logprobs);
   m.impl("skinny_linear", &skinny_linear);
   m.impl("skinny2_linear", &skinny2_linear);

@@ -137,6 +137,28 @@ void launch_sample(
     uint64_t* partials, int n_split,   // [batch, n_split] workspace
     hipStream_t stream);
 
+// Constrained sampling of selected rows: z = float(logit) + bias, keep
+// z >= k-th largest z (ties stay; k == 0 or k >= vocab: off) and
+// z >= z_max + T*ln(min_p) (0: off), then the sampler's own Gumbel-max /
+// greedy arg-max over what is kept.  temperatures/seeds are indexed by
+// rows[r]; top_k, min_p and the CSR bias list (ids ascending per row) by
+// r.  The logits are only read; no workspace (sampling.hip).
+int sample_constrained_max_vocab();
+void launch_sample_constrained(
+    const uint16_t* logits,            // [batch, vocab] bf16
+    const int32_t* rows,               // [n_rows] row indices into logits
+    const float* temperatures,         // [batch]
+    const uint64_t* seeds,             // [batch]
+    uint64_t step,
+    const int32_t* top_k,              // [n_rows]
+    const float* min_p,                // [n_rows]
+    const int32_t* bias_offsets,       // [n_rows + 1]
+    const int32_t* bias_ids,           // [n_bias_total]
+    const float* bias_vals,            // [n_bias_total]
+    int n_bias_total,
+    int32_t* out_tokens,               // [n_rows]
+    int n_rows, int vocab, hipStream_t stream);
+
 // Fused log-softmax value of one emitted token per selected row plus the
 // row's k most likely tokens (value descending, index ascending on ties),
 // computed on the RAW logits — one pass over the selected rows, nothing

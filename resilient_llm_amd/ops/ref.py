@@ -169,6 +169,54 @@ def sample(logits: torch.Tensor, temperatures: torch.Tensor,
     return out
 
 
+def sample_constrained(logits: torch.Tensor, rows: torch.Tensor,
+                       temperatures: torch.Tensor, seeds: torch.Tensor,
+                       step: int, top_k: torch.Tensor, min_p: torch.Tensor,
+                       bias_offsets: torch.Tensor, bias_ids: torch.Tensor,
+                       bias_vals: torch.Tensor) -> torch.Tensor:
+    """``sample`` under logit_bias / top_k / min_p for the selected rows.
+    z = float(logit) + bias in fp32; kept = {z >= k-th largest z} (ties
+    stay; k == 0 or k >= vocab off) & {z >= z_max + T*ln(min_p)} (0 off).
+    Greedy rows are exact (arg-max z, lowest index); stochastic rows draw
+    from softmax(z/T) renormalised over the kept set with a torch
+    generator seeded per row from (seeds[rows[r]], step) — the kernel's
+    reproducibility contract, not its stream."""
+    R = rows.numel()
+    if not (top_k.numel() == R and min_p.numel() == R
+            and bias_offsets.numel() == R + 1):
+        raise ValueError("rows/top_k/min_p/bias_offsets length mismatch")
+    if bias_ids.numel() != bias_vals.numel():
+        raise ValueError("bias_ids/bias_vals length mismatch")
+    V = logits.shape[1]
+    out = torch.empty(R, dtype=torch.int32, device=logits.device)
+    offs = bias_offsets.tolist()
+    C = 0x9e3779b97f4a7c15
+    for r, row in enumerate(rows.tolist()):
+        z = logits[row].float()
+        b0, b1 = offs[r], offs[r + 1]
+        if b1 > b0:
+            z = z.clone()
+            z[bias_ids[b0:b1].long()] += bias_vals[b0:b1].float()
+        T = float(temperatures[row])
+        if T <= 0:
+            out[r] = int(z.argmax())
+            continue
+        keep = torch.ones(V, dtype=torch.bool, device=z.device)
+        k = int(top_k[r])
+        if 1 <= k < V:
+            keep &= z >= z.topk(k).values[-1]
+        m = float(min_p[r])
+        if m > 0:
+            keep &= z >= z.max() + torch.tensor(T, dtype=torch.float32) \
+                * torch.log(torch.tensor(m, dtype=torch.float32))
+        probs = torch.softmax(
+            torch.where(keep, z, z.new_tensor(float("-inf"))) / T, dim=-1)
+        gen = torch.Generator(device=logits.device)
+        gen.manual_seed((int(seeds[row]) + C * step) & 0x7fffffffffffffff)
+        out[r] = int(torch.multinomial(probs, 1, generator=gen))
+    return out
+
+
 def token_logprobs(logits: torch.Tensor, rows: torch.Tensor,
                    tokens: torch.Tensor, k: int):
     """Log-softmax (fp32, RAW logits — independent of temperature, top-p

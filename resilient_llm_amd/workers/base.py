@@ -54,6 +54,11 @@ class GenerationRequest:
     stop: Optional[list] = None      # OpenAI stop sequences (<= 4 strings)
     logprobs: bool = False           # OpenAI logprobs / top_logprobs (0..20)
     top_logprobs: int = 0
+    # OpenAI logit_bias as [[token_id, bias], ...] ascending by id, and
+    # the top_k / min_p sampling filters (0 = off)
+    logit_bias: Optional[list] = None
+    top_k: int = 0
+    min_p: float = 0.0
 
 
 @dataclasses.dataclass

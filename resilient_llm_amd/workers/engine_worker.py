@@ -285,6 +285,12 @@ class EngineWorker(Worker):
                  mode: str = "stream") -> tuple[str, asyncio.Queue, int]:
         self._check_fault()
         prompt_ids = self.tokenizer.encode(render_prompt(req.messages))
+        # a bias id past the serving model's vocab names no token of it:
+        # biasing it is a no-op, not a worker failure (which would put
+        # the worker in cooldown and fail the request over)
+        vocab = getattr(self.engine.model.config, "vocab_size", None)
+        logit_bias = [[int(t), float(b)] for t, b in req.logit_bias or ()
+                      if not vocab or int(t) < vocab] or None
         params = SamplingParams(max_tokens=req.max_tokens,
                                 temperature=req.temperature,
                                 top_p=req.top_p,
@@ -292,7 +298,10 @@ class EngineWorker(Worker):
                                 frequency_penalty=req.frequency_penalty,
                                 seed=req.seed,
                                 logprobs=req.logprobs,
-                                top_logprobs=req.top_logprobs)
+                                top_logprobs=req.top_logprobs,
+                                logit_bias=logit_bias,
+                                top_k=req.top_k,
+                                min_p=req.min_p)
         self._req_counter += 1
         rid = f"{req.request_id}-{self._req_counter}"
         q: asyncio.Queue = asyncio.Queue()
