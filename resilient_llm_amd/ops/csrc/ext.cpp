@@ -253,6 +253,17 @@ static SplitScratch make_split_scratch(const Tensor& ref, int batch,
   return s;
 }
 
+// Introspection for tests: the split factor decode_attn /
+// decode_attn_qkv / decode_attn_rope_qkv run with at this (batch, n_kv).
+// It asks make_split_scratch itself (group = D = 1: a few host floats),
+// so it cannot drift from what the ops do.
+int64_t decode_attn_split(int64_t batch, int64_t n_kv) {
+  TORCH_CHECK(batch >= 1 && n_kv >= 1 && batch * n_kv < (int64_t(1) << 24),
+              "bad batch/n_kv");
+  const Tensor host = at::empty({0}, at::TensorOptions().dtype(at::kFloat));
+  return make_split_scratch(host, int(batch), int(n_kv), 1, 1).n_split;
+}
+
 // ---------------------------------------------------------- decode_attn
 Tensor decode_attn(const Tensor& q, const Tensor& k_cache,
                    const Tensor& v_cache, const Tensor& block_table,
@@ -711,6 +722,7 @@ TORCH_LIBRARY(rlli, m) {
         "Tensor slot_mapping) -> ()");
   m.def("decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, "
         "Tensor block_table, Tensor seq_lens, float scale) -> Tensor");
+  m.def("decode_attn_split(int batch, int n_kv) -> int", &decode_attn_split);
   m.def("rope_kv_append_qkv_(Tensor(a!) qkv, Tensor positions, Tensor cos_sin, "
         "Tensor(b!) k_cache, Tensor(c!) v_cache, Tensor slot_mapping, "
         "int n_q) -> ()");

@@ -51,6 +51,10 @@ void launch_rope_kv_append(
 int decode_attn_n_split(int batch, int n_kv_heads);
 
 // Paged GQA decode attention: one new q token per sequence.
+// Contract: cache slots past seq_len must hold finite values (masked
+// tokens weigh p = 0 but their V is still multiplied, so 0 * NaN/Inf
+// would propagate; a zero-initialised cache only ever receives finite
+// values).
 void launch_decode_attn(
     const uint16_t* q,                 // [batch, n_q_heads, head_dim]
     const void* k_cache,               // [blocks, n_kv, block_size, head_dim]
