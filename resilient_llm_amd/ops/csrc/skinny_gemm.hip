@@ -183,6 +183,9 @@ void launch_skinny_gemm(const uint16_t* x, const uint16_t* w, float* ws,
                       atoi(std::getenv("RLLI_SKINNY_WDEPTH")) == 1) ? 1 : 2;
   const int total_chunks = K / KC;
   const int chunks_per_slice = (total_chunks + splitk - 1) / splitk;
+  // rounding can leave trailing slices with no chunk: drop them, or the
+  // reduce would sum their UNINITIALIZED slabs (ws may stay oversized)
+  splitk = (total_chunks + chunks_per_slice - 1) / chunks_per_slice;
   const int blocks = (N / BN) * splitk;
   auto launch = [&](auto mt_tag) {
     constexpr int MT = decltype(mt_tag)::value;
