@@ -94,6 +94,7 @@ class _Completions:
                logprobs: bool = False, top_logprobs: Optional[int] = None,
                logit_bias: Optional[dict] = None,
                top_k: Optional[int] = None, min_p: Optional[float] = None,
+               n: Optional[int] = None,
                extra_headers: Optional[dict] = None, **kw):
         payload = {"model": model, "messages": messages, "max_tokens": max_tokens,
                    "temperature": temperature, "top_p": top_p, "stream": stream}
@@ -114,6 +115,10 @@ class _Completions:
             payload["top_k"] = top_k
         if min_p is not None:
             payload["min_p"] = min_p
+        # n choices (1..16, non-streaming): choices[i].index = i, usage
+        # counts the prompt once
+        if n is not None:
+            payload["n"] = n
         payload.update(kw)
         if stream:
             return self._client._post_stream("/chat/completions", payload,

@@ -101,6 +101,14 @@ class SeqState:
     default_seed: int = 0                  # deterministic per arrival order
     n_cached: int = 0
     arrived_at: float = dataclasses.field(default_factory=time.monotonic)
+    # n > 1 choices (add_request_group): the leader of a group that has
+    # not forked yet carries members 1..n-1 here (each holding its private
+    # block reservation once admitted); None for every other sequence,
+    # the leader itself included from the fork on
+    children: Optional[list] = None
+    # group leader aborted before the fork: keeps prefilling for its
+    # children, emits nothing and is freed at the fork
+    silent: bool = False
 
     def blocks_needed(self, block_size: int) -> int:
         return -(-(len(self.prompt_ids) + self.params.max_tokens) // block_size)
@@ -173,6 +181,12 @@ class LLMEngine:
         self.block_size = kv_cache.block_size
         self._aborted: set[str] = set()
         self._live: set[str] = set()   # rids currently owned by the engine
+        # n > 1 groups: rids of members 1..n-1 still attached to a leader
+        # that has not forked (in no pool of their own yet), and how many
+        # of them sit behind a WAITING leader (they count against
+        # max_queue); both change only under the queue lock
+        self._attached: set[str] = set()
+        self._waiting_attached = 0
         # live migration (SURVEY.md §5.8 state-migration): extraction and
         # adoption are queued control ops executed BETWEEN steps on the
         # engine thread — the only thread that may touch KV/seq state
@@ -195,6 +209,9 @@ class LLMEngine:
                       # = kernel + tolist sync): finds host-bound stalls
                       "prefill_prep_time": 0.0, "prefill_fwd_time": 0.0,
                       "prefill_sample_time": 0.0,
+                      # n > 1 groups: sequences forked off a leader, and
+                      # the prompt blocks they share instead of owning
+                      "forks": 0, "fork_shared_blocks": 0,
                       "admit_events": []}
         # decode graph runner installed by engine/graph.py (GPU only)
         self.graph_runner = None
@@ -206,16 +223,19 @@ class LLMEngine:
     # ------------------------------------------------------------- admin
     @property
     def n_active(self) -> int:
-        return len(self.waiting) + len(self.prefilling) + len(self.running)
+        return (len(self.waiting) + len(self.prefilling) + len(self.running)
+                + len(self._attached))
 
     def has_work(self) -> bool:
         return bool(self.waiting or self.prefilling or self.running
                     or self._pending or self._adopt_queue
                     or self._extract_reqs)
 
-    def add_request(self, req_id: str, prompt_ids: list,
-                    params: Optional[SamplingParams] = None) -> None:
-        params = params or SamplingParams()
+    def _validate(self, prompt_ids: list,
+                  params: SamplingParams) -> SamplingParams:
+        """The API-boundary checks every admitted sequence passes
+        (add_request and each member of add_request_group); returns the
+        params, with logit_bias normalised to ascending ids."""
         if not 0 <= params.top_logprobs <= 20:
             raise ValueError(
                 f"top_logprobs must be in 0..20, got {params.top_logprobs}")
@@ -250,7 +270,12 @@ class LLMEngine:
                 raise ValueError(
                     f"prompt token id out of range [0, {vocab}): "
                     f"min={lo} max={hi}")
-        if len(self.waiting) >= self.max_queue:
+        return params
+
+    def add_request(self, req_id: str, prompt_ids: list,
+                    params: Optional[SamplingParams] = None) -> None:
+        params = self._validate(prompt_ids, params or SamplingParams())
+        if len(self.waiting) + self._waiting_attached >= self.max_queue:
             raise CapacityExceeded(f"queue full ({self.max_queue})")
         seq = SeqState(req_id=req_id, prompt_ids=list(prompt_ids), params=params)
         self._arrival_counter += 1
@@ -270,6 +295,60 @@ class LLMEngine:
         with self._queue_lock:
             self.waiting.append(seq)
             self._live.add(req_id)
+
+    def add_request_group(self, req_ids: list, prompt_ids: list,
+                          params_list: list) -> None:
+        """Admit ONE prompt with n = len(req_ids) continuations (OpenAI
+        ``n``), each with its own SamplingParams and reported under its
+        own req_id.  Member 0 (the leader) prefills the prompt once; in
+        the step its last chunk completes the others fork off it: they
+        share its full prompt blocks by refcount, get a private copy of
+        the partial last block, and sample their first token from the
+        leader's last-row logits with their own params and seed.  From
+        there every member is an ordinary sequence."""
+        n = len(req_ids)
+        if n < 1 or len(params_list) != n or len(set(req_ids)) != n:
+            raise ValueError("add_request_group needs n >= 1 distinct "
+                             "req_ids and one SamplingParams per member")
+        params_list = [self._validate(prompt_ids, p or SamplingParams())
+                       for p in params_list]
+        if n > self.max_batch_size:
+            raise CapacityExceeded(
+                f"n = {n} exceeds max_batch_size {self.max_batch_size}")
+        if len(self.waiting) + self._waiting_attached + n > self.max_queue:
+            raise CapacityExceeded(f"queue full ({self.max_queue})")
+        F = len(prompt_ids) // self.block_size
+        seqs = []
+        total_blocks = 0
+        for i, (rid, params) in enumerate(zip(req_ids, params_list)):
+            seq = SeqState(req_id=rid, prompt_ids=list(prompt_ids),
+                           params=params)
+            if len(seq.prompt_ids) + params.max_tokens > self.max_model_len:
+                raise CapacityExceeded(
+                    f"prompt+max_tokens = "
+                    f"{len(seq.prompt_ids) + params.max_tokens} exceeds "
+                    f"max_model_len {self.max_model_len}")
+            total_blocks += seq.blocks_needed(self.block_size) \
+                - (F if i else 0)
+            seqs.append(seq)
+        if total_blocks > self.kv.num_blocks:
+            raise CapacityExceeded(
+                f"group needs {total_blocks} KV blocks, cache has "
+                f"{self.kv.num_blocks}")
+        for seq in seqs:
+            self._arrival_counter += 1
+            seq.default_seed = (self.seed * 1000003
+                                + self._arrival_counter) & 0x7fffffffffffffff
+        leader = seqs[0]
+        leader.children = seqs[1:]
+        if self.enable_prefix_caching:
+            leader.block_keys = block_hash_chain(leader.prompt_ids,
+                                                 self.block_size)
+        with self._queue_lock:
+            self.waiting.append(leader)
+            self._live.update(req_ids)
+            self._attached.update(req_ids[1:])
+            self._waiting_attached += n - 1
 
     def abort(self, req_id: str) -> None:
         """Abort is a no-op for rids the engine no longer owns (finished /
@@ -293,11 +372,22 @@ class LLMEngine:
                 + len(self.prefilling) < self.max_batch_size):
             return admitted
         tokens = 0
-        while (self.waiting
-               and len(self.running) + len(self.prefilling) + len(admitted)
-               < self.max_batch_size):
+        # batch slots in use: an unforked group leader holds one per
+        # attached member as well
+        used = len(self.running) + len(self.prefilling) + sum(
+            len(s.children) for s in self.prefilling if s.children)
+        while self.waiting and used < self.max_batch_size:
             seq = self.waiting[0]
-            if seq.req_id in self._aborted:
+            if seq.children is not None:
+                # group: members aborted while queued leave here; an
+                # aborted leader with survivors becomes their carrier
+                self._prune_group_locked(seq, waiting=True)
+                if seq.silent and not seq.children:
+                    self.waiting.popleft()
+                    continue
+                if used + 1 + len(seq.children) > self.max_batch_size:
+                    break              # all-or-nothing: the group waits whole
+            elif seq.req_id in self._aborted:
                 self.waiting.popleft()
                 self._aborted.discard(seq.req_id)
                 self._live.discard(seq.req_id)
@@ -316,18 +406,60 @@ class LLMEngine:
                 # speculative verification writes KV up to spec_lookup
                 # positions past the committed length
                 needed += -(-self.spec_lookup // self.block_size)
-            if needed > self.kv.free_blocks:
+            # group members share the leader's full prompt blocks: each
+            # reserves only what it will write itself (tail + outputs)
+            child_needs = []
+            if seq.children:
+                F = len(seq.prompt_ids) // self.block_size
+                spec = -(-self.spec_lookup // self.block_size) \
+                    if self.spec_lookup else 0
+                child_needs = [c.blocks_needed(self.block_size) - F + spec
+                               for c in seq.children]
+            if needed + sum(child_needs) > self.kv.free_blocks:
                 if reused:
                     self.kv.free(reused)
                 break
             seq.blocks = reused + self.kv.allocate(needed)
+            for c, nb in zip(seq.children or (), child_needs):
+                c.blocks = self.kv.allocate(nb)
             seq.n_cached = len(reused) * self.block_size
             tokens += len(seq.prompt_ids) - seq.n_cached
             admitted.append(self.waiting.popleft())
+            used += 1
+            if seq.children:
+                used += len(seq.children)
+                self._waiting_attached -= len(seq.children)
         if admitted and len(self.stats["admit_events"]) < 1000:
             self.stats["admit_events"].append(
                 (round(time.monotonic(), 4), len(admitted), len(self.waiting)))
         return admitted
+
+    def _prune_group_locked(self, leader: SeqState,
+                            waiting: bool = False) -> None:
+        """Apply pending aborts to a group that has not forked (queue lock
+        held): an aborted member 1..n-1 leaves and its reservation is
+        freed; an aborted leader turns into a silent carrier, which only
+        survives while a member is left to fork off it."""
+        if not self._aborted:
+            return
+        keep = []
+        for c in leader.children:
+            if c.req_id in self._aborted:
+                if c.blocks:
+                    self.kv.free(c.blocks)
+                    c.blocks = []
+                self._aborted.discard(c.req_id)
+                self._live.discard(c.req_id)
+                self._attached.discard(c.req_id)
+                if waiting:
+                    self._waiting_attached -= 1
+            else:
+                keep.append(c)
+        leader.children = keep
+        if leader.req_id in self._aborted:
+            leader.silent = True
+            self._aborted.discard(leader.req_id)
+            self._live.discard(leader.req_id)
 
     def _slot(self, seq: SeqState, pos: int) -> int:
         return seq.blocks[pos // self.block_size] * self.block_size \
@@ -445,7 +577,17 @@ class LLMEngine:
         for attr in ("running", "prefilling"):
             keep = []
             for seq in getattr(self, attr):
-                if seq.req_id in self._aborted:
+                if seq.children is not None:
+                    # unforked group: aborted members leave; the leader
+                    # stays (silent if aborted) while one is left
+                    with self._queue_lock:
+                        self._prune_group_locked(seq)
+                    if seq.silent and not seq.children:
+                        self.kv.free(seq.blocks)
+                        seq.blocks = []
+                    else:
+                        keep.append(seq)
+                elif seq.req_id in self._aborted:
                     self.kv.free(seq.blocks)
                     seq.blocks = []
                     self._aborted.discard(seq.req_id)
@@ -492,6 +634,17 @@ class LLMEngine:
             rids = self._extract_reqs
             self._extract_reqs = set()
         for rid in rids:
+            # a member of an n > 1 group that has not forked cannot leave
+            # alone: report "missing" and leave the group intact
+            with self._queue_lock:
+                unforked = rid in self._attached or any(
+                    s.req_id == rid and s.children is not None
+                    for pool in (self.prefilling, self.waiting)
+                    for s in pool)
+                if unforked:
+                    self._extracted[rid] = "missing"
+            if unforked:
+                continue
             state = None
             for attr in ("running", "prefilling", "waiting"):
                 pool = getattr(self, attr)
@@ -912,9 +1065,58 @@ class LLMEngine:
         return self._mixed_finish(chunk_plan, sampled_seqs, logits,
                                   decode_seqs=seqs_d)
 
+    def _fork_groups(self, sampled_seqs: list, logits: torch.Tensor):
+        """Fork every n > 1 group whose leader's prompt completed in this
+        step.  Each member 1..n-1 takes a reference on the leader's full
+        prompt blocks ahead of its private ones and a copy of the partial
+        last block (ONE copy_blocks call for the step, stream-ordered
+        after the forward that wrote the leader's KV), and gets a row of
+        its own — the leader's last-row logits repeated — directly after
+        the leader, so sampling, logprobs and the constrained sampler
+        serve it with its own params and seed like any other row.
+        Returns (sampled_seqs, logits, silent leaders to free)."""
+        bs = self.block_size
+        rows: list[int] = []
+        seqs: list[SeqState] = []
+        silent: list[SeqState] = []
+        src: list[int] = []
+        dst: list[int] = []
+        for r, seq in enumerate(sampled_seqs):
+            if seq.silent:
+                silent.append(seq)
+            else:
+                rows.append(r)
+                seqs.append(seq)
+            if seq.children is None:
+                continue
+            n_prompt = len(seq.prompt_ids)
+            F = n_prompt // bs
+            for c in seq.children:
+                c.blocks = self.kv.share(seq.blocks[:F]) + c.blocks
+                if n_prompt % bs:
+                    src.append(seq.blocks[F])
+                    dst.append(c.blocks[F])
+                c.n_cached = n_prompt
+                rows.append(r)
+                seqs.append(c)
+            self.stats["forks"] += len(seq.children)
+            self.stats["fork_shared_blocks"] += F * len(seq.children)
+            with self._queue_lock:
+                self._attached.difference_update(
+                    c.req_id for c in seq.children)
+            seq.children = None
+        self.kv.copy_blocks(src, dst)
+        logits = logits.index_select(
+            0, torch.tensor(rows, dtype=torch.long, device=logits.device))
+        return seqs, logits, silent
+
     def _mixed_finish(self, chunk_plan, sampled_seqs, logits,
                       decode_seqs=()) -> tuple[int, list[StepOutput]]:
         t_s = time.monotonic()
+        silent: list[SeqState] = []
+        if any(s.children is not None for s in sampled_seqs):
+            sampled_seqs, logits, silent = self._fork_groups(sampled_seqs,
+                                                             logits)
         tokens = self._sample(logits, sampled_seqs)
         plan = self._lp_plan(sampled_seqs)
         recs = {}
@@ -943,6 +1145,9 @@ class LLMEngine:
             seq.output_ids.append(tok)
             if not self._finish(seq, outs, tok, recs.get(row)):
                 still_running.append(seq)
+        for seq in silent:             # carriers: their children hold on
+            self.kv.free(seq.blocks)   # to the shared prompt blocks
+            seq.blocks = []
         self.running = [s for s in self.running
                         if id(s) not in decode_set] + still_running
         done = {id(s) for s, start, n in chunk_plan

@@ -29,6 +29,8 @@ exceed the capture envelope (very long sequences) decode eager.
 
 from __future__ import annotations
 
+import gc
+
 import torch
 
 from .. import ops
@@ -112,17 +114,31 @@ class DecodeGraphRunner:
         torch.cuda.current_stream(self.device).wait_stream(s)
         torch.cuda.synchronize(self.device)
 
-        # capture largest-first so the shared pool is sized once
-        for b in sorted(self.buckets, reverse=True):
-            g = torch.cuda.CUDAGraph()
-            if self._pool is None:
-                with torch.cuda.graph(g):
-                    self.logits[b], self.tokens[b] = self._steady_body(b)
-                self._pool = g.pool()
-            else:
-                with torch.cuda.graph(g, pool=self._pool):
-                    self.logits[b], self.tokens[b] = self._steady_body(b)
-            self.graphs[b] = g
+        # No garbage collection inside a capture: a runner is in a
+        # reference cycle with its engine, so a DEAD runner (an earlier
+        # engine of this process) is only finalized by the collector, and
+        # destroying its graphs and pool while another capture is open
+        # aborts the process.  torch.cuda.graph no longer collects on
+        # entry, so collect once here, then hold the collector off until
+        # the last capture has ended.
+        gc.collect()
+        gc_was_enabled = gc.isenabled()
+        gc.disable()
+        try:
+            # capture largest-first so the shared pool is sized once
+            for b in sorted(self.buckets, reverse=True):
+                g = torch.cuda.CUDAGraph()
+                if self._pool is None:
+                    with torch.cuda.graph(g):
+                        self.logits[b], self.tokens[b] = self._steady_body(b)
+                    self._pool = g.pool()
+                else:
+                    with torch.cuda.graph(g, pool=self._pool):
+                        self.logits[b], self.tokens[b] = self._steady_body(b)
+                self.graphs[b] = g
+        finally:
+            if gc_was_enabled:
+                gc.enable()
         torch.cuda.synchronize(self.device)
         # the warmup/captures advanced the state buffers; a load() must
         # precede the first real step()

@@ -21,6 +21,8 @@ import struct
 
 import torch
 
+from .. import ops
+
 
 class OutOfBlocks(RuntimeError):
     """KV budget exhausted — the worker surfaces this as Throttled (X13)."""
@@ -103,6 +105,29 @@ class PagedKVCache:
                 self._cached_free[b] = None     # evictable but reusable
             else:
                 self._free.append(b)
+
+    # ------------------------------------------------------ copy-on-fork
+    def share(self, blocks: list[int]) -> list[int]:
+        """Take one more reference on blocks that are already live (a
+        forked sequence reading its parent's full prompt blocks); each
+        holder frees them as usual.  Returns ``blocks`` as a new list."""
+        for b in blocks:
+            assert self._ref[b] > 0, f"share of a free block {b}"
+            self._ref[b] += 1
+        return list(blocks)
+
+    def copy_blocks(self, src_ids: list[int], dst_ids: list[int]) -> None:
+        """cache[l, dst] = cache[l, src] for every layer, K and V, in one
+        stream-ordered launch (ops.kv_copy_blocks_): gives each forked
+        sequence its own writable copy of the parent's partial block."""
+        assert len(src_ids) == len(dst_ids)
+        if not src_ids:
+            return
+        dev = self.k.device
+        ops.kv_copy_blocks_(
+            self.k, self.v,
+            torch.tensor(src_ids, dtype=torch.int32, device=dev),
+            torch.tensor(dst_ids, dtype=torch.int32, device=dev))
 
     # -------------------------------------------------------- prefix cache
     def lookup_prefix(self, keys: list[bytes]) -> list[int]:

@@ -23,6 +23,7 @@ SURVEY.md §2.2 in one place:
 from __future__ import annotations
 
 import asyncio
+import dataclasses
 import json
 import time
 import uuid
@@ -42,6 +43,7 @@ from ..workers.base import (
 from .http import Request, Response
 
 DEFAULT_MAX_TOKENS = 128
+MAX_N_CHOICES = 16          # OpenAI n: choices per request
 STREAM_CHUNK_TIMEOUT_S = 30.0
 REQUEST_TIMEOUT_S = 120.0
 
@@ -406,16 +408,29 @@ class GatewayApp:
                                   or not isinstance(min_p, (int, float))
                                   or not 0 <= min_p <= 1):
             raise ValueError("'min_p' must be a number in [0, 1]")
+        # OpenAI n: choices per request, 1..16.  Greedy requests yield n
+        # identical choices, as OpenAI does.
+        n = body.get("n")
+        if n is not None:
+            if isinstance(n, bool) or not isinstance(n, int) \
+                    or not 1 <= n <= MAX_N_CHOICES:
+                raise ValueError(
+                    f"'n' must be an integer in 1..{MAX_N_CHOICES}")
+            if n > 1 and body.get("stream"):
+                raise ValueError(
+                    "'n' > 1 is not supported with 'stream': true; send "
+                    "'n' without streaming or stream one choice per request")
         return body
 
-    def _estimate(self, body: dict) -> tuple[int, int]:
+    def _estimate(self, body: dict, n: int = 1) -> tuple[int, int]:
         cpt = self.config.router.estimate_chars_per_token
         prompt_est = sum(max(1, len(str(m.get("content", ""))) // cpt)
                          for m in body["messages"])
         max_tokens = int(body.get("max_tokens")
                        or body.get("max_completion_tokens")
                        or DEFAULT_MAX_TOKENS)
-        return prompt_est, prompt_est + max_tokens
+        # n choices share one prompt; each may run to max_tokens
+        return prompt_est, prompt_est + n * max_tokens
 
     def _gen_request(self, body: dict, consumer: str, ticket: Ticket,
                      stream: bool, rid: Optional[str] = None) -> GenerationRequest:
@@ -473,7 +488,8 @@ class GatewayApp:
             return Response.error(403, f"api key not permitted for model "
                                        f"{alias!r}", err_type="permission_error",
                                   code="model_access_denied")
-        prompt_est, total_est = self._estimate(body)
+        n = int(body.get("n") or 1)
+        prompt_est, total_est = self._estimate(body, n)
         if not self.consumers.try_acquire(consumer, total_est):
             return Response.error(429, f"consumer {consumer!r} rate limit exceeded",
                                   err_type="rate_limit_error", code="rate_limit_exceeded")
@@ -493,6 +509,8 @@ class GatewayApp:
         if bool(body.get("stream")):
             return await self._chat_stream(body, alias, consumer, total_est,
                                            rid)
+        if n > 1:
+            return await self._chat_n(body, alias, consumer, total_est, rid, n)
         return await self._chat_once(body, alias, consumer, total_est, rid)
 
     async def text_completions(self, req: Request) -> Response:
@@ -535,30 +553,33 @@ class GatewayApp:
         if resp.status != 200:
             return resp
         payload = json.loads(resp.body)
-        text = payload["choices"][0]["message"]["content"]
-        legacy_lp = None
-        if n_lp is not None:
-            entries = (payload["choices"][0].get("logprobs")
-                       or {}).get("content") or []
-            offsets, pos = [], 0
-            for e in entries:
-                offsets.append(pos)
-                pos += len(e["token"])
-            legacy_lp = {
-                "tokens": [e["token"] for e in entries],
-                "token_logprobs": [e["logprob"] for e in entries],
-                "top_logprobs": [{t["token"]: t["logprob"]
-                                  for t in e["top_logprobs"]}
-                                 for e in entries],
-                "text_offset": offsets,
-            }
+        choices = []
+        for ch in payload["choices"]:      # one per 'n'
+            legacy_lp = None
+            if n_lp is not None:
+                entries = (ch.get("logprobs") or {}).get("content") or []
+                offsets, pos = [], 0
+                for e in entries:
+                    offsets.append(pos)
+                    pos += len(e["token"])
+                legacy_lp = {
+                    "tokens": [e["token"] for e in entries],
+                    "token_logprobs": [e["logprob"] for e in entries],
+                    "top_logprobs": [{t["token"]: t["logprob"]
+                                      for t in e["top_logprobs"]}
+                                     for e in entries],
+                    "text_offset": offsets,
+                }
+            choices.append({"index": ch["index"],
+                            "text": ch["message"]["content"],
+                            "logprobs": legacy_lp,
+                            "finish_reason": ch["finish_reason"]})
         out = {
             "id": payload["id"].replace("chatcmpl-", "cmpl-", 1),
             "object": "text_completion",
             "created": payload["created"],
             "model": payload["model"],
-            "choices": [{"index": 0, "text": text, "logprobs": legacy_lp,
-                         "finish_reason": payload["choices"][0]["finish_reason"]}],
+            "choices": choices,
             "usage": payload["usage"],
         }
         return Response.json_response(out, headers=resp.headers)
@@ -646,6 +667,99 @@ class GatewayApp:
         # no backend work happened: release the consumer's token charge
         # (failed attempts over-throttled clients for a full
         # minute window during backend outages)
+        self.consumers.reconcile(consumer, total_est, 0)
+        msg = sanitize_error(last_err) if last_err else "no deployment available"
+        status = 429 if isinstance(last_err, WorkerThrottled) else 502
+        return Response.error(status, f"all deployments failed: {msg}",
+                              err_type="api_error")
+
+    @staticmethod
+    def _choice_seed(seed: Optional[int], i: int) -> Optional[int]:
+        """Seed of choice ``i`` of an n > 1 request: choice 0 keeps the
+        request's seed (it equals the n = 1 response), the others derive
+        theirs from it — fixed per (seed, i), so a failover replay of the
+        whole group regenerates every choice identically."""
+        if seed is None or i == 0:
+            return seed
+        import hashlib
+        return int.from_bytes(
+            hashlib.blake2b(f"{seed}:{i}".encode(), digest_size=8).digest(),
+            "big") >> 1
+
+    async def _chat_n(self, body: dict, alias: str, consumer: str,
+                      total_est: int, rid: str, n: int) -> Response:
+        """n > 1 choices: ONE router ticket (sized prompt + n*max_tokens)
+        and ONE worker.generate_n call, so an engine worker prefills the
+        prompt once and forks the choices off it.  Same failover loop as
+        _chat_once: a worker failure or migration re-routes the whole
+        group, and the per-choice seeds make the replay deterministic."""
+        t0 = time.monotonic()
+        exclude: set = set()
+        last_err: Optional[Exception] = None
+        try:
+            attempts = self._max_attempts(alias)
+        except UnknownAlias:
+            self.consumers.reconcile(consumer, total_est, 0)
+            return Response.error(404, f"unknown model {alias!r}",
+                                  err_type="invalid_request_error", code="model_not_found")
+        for _ in range(attempts):
+            try:
+                ticket = self.router.acquire(alias, total_est, exclude=exclude,
+                                             affinity_key=self._affinity_key(body))
+            except RouterRateLimit as e:
+                if last_err is not None and not isinstance(last_err, WorkerThrottled):
+                    break
+                self.consumers.reconcile(consumer, total_est, 0)
+                return Response.error(429, str(e), err_type="rate_limit_error",
+                                      code="rate_limit_exceeded")
+            greq = self._gen_request(body, consumer, ticket, stream=False,
+                                     rid=rid)
+            greqs = [dataclasses.replace(
+                greq, request_id=f"{rid}.c{i}",
+                seed=self._choice_seed(greq.seed, i)) for i in range(n)]
+            try:
+                worker = self._worker_for(ticket)
+                results = await asyncio.wait_for(worker.generate_n(greqs),
+                                                 timeout=REQUEST_TIMEOUT_S)
+            except WorkerMigrated:
+                self.router.complete(ticket, actual_tokens=0)
+                exclude.add(id(ticket.state))
+                continue
+            except (WorkerError, asyncio.TimeoutError) as e:
+                last_err = e
+                throttled = isinstance(e, WorkerThrottled)
+                self.router.fail(ticket, charge=throttled)
+                self._record(ticket, greq, consumer,
+                             "throttled" if throttled else "error", t0)
+                exclude.add(id(ticket.state))
+                continue
+            # the prompt is counted once, the completions summed; one
+            # charge and one ledger row for the HTTP request
+            ttfts = [r.ttft_ms for r in results if r.ttft_ms is not None]
+            total = GenerationResult(
+                text="", prompt_tokens=results[0].prompt_tokens,
+                completion_tokens=sum(r.completion_tokens for r in results),
+                ttft_ms=min(ttfts) if ttfts else None)
+            actual = total.prompt_tokens + total.completion_tokens
+            self.router.complete(ticket, actual_tokens=actual)
+            self.consumers.reconcile(consumer, total_est, actual)
+            self._record(ticket, greq, consumer, "ok", t0, total, worker.device)
+            resp = self._completion_response(greq, ticket, results[0], worker)
+            payload = json.loads(resp.body)
+            for i, r in enumerate(results[1:], 1):
+                choice = {"index": i,
+                          "message": {"role": "assistant", "content": r.text},
+                          "finish_reason": r.finish_reason}
+                if greq.logprobs:
+                    choice["logprobs"] = {"content": r.logprobs or []}
+                payload["choices"].append(choice)
+            payload["usage"] = {
+                "prompt_tokens": total.prompt_tokens,
+                "completion_tokens": total.completion_tokens,
+                "total_tokens": actual,
+            }
+            return Response.json_response(payload, headers=resp.headers)
+        from ..utils.logging import sanitize_error
         self.consumers.reconcile(consumer, total_est, 0)
         msg = sanitize_error(last_err) if last_err else "no deployment available"
         status = 429 if isinstance(last_err, WorkerThrottled) else 502

@@ -237,6 +237,21 @@ def token_logprobs(logits: torch.Tensor, rows: torch.Tensor,
     return ref.token_logprobs(logits, rows, tokens, k)
 
 
+def kv_copy_blocks_(k_cache: torch.Tensor, v_cache: torch.Tensor,
+                    src: torch.Tensor, dst: torch.Tensor) -> None:
+    """Fork copy on the paged cache: for every layer l and pair p,
+    ``cache[l, dst[p]] = cache[l, src[p]]`` for both [L, NB, H, bs, D]
+    caches — in place, bit-exact, one launch, any 1/2/4-byte element.
+    ``src`` / ``dst`` are int32 tensors on the cache's device; ``src`` may
+    repeat, ``dst`` entries are unique and disjoint from ``src`` (the
+    caller's contract).  Every other block is untouched."""
+    if k_cache.is_cuda:
+        _gpu()
+        torch.ops.rlli.kv_copy_blocks_(k_cache, v_cache, src, dst)
+    else:
+        ref.kv_copy_blocks_(k_cache, v_cache, src, dst)
+
+
 def prefill_paged_attn(qkv, k_cache, v_cache, chunk_row0, chunk_pos0,
                        chunk_nrows, chunk_btrow, block_tables,
                        scale: float, n_q: int) -> torch.Tensor:

@@ -42,6 +42,7 @@ SOURCES = [
     "prefill_paged.hip",
     "sampling.hip",
     "logprobs.hip",
+    "kv_copy.hip",
     "skinny_gemm.hip",
     "skinny2.hip",
     "streamprobe.hip",

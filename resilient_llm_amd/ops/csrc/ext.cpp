@@ -708,6 +708,48 @@ std::tuple<Tensor, Tensor, Tensor> token_logprobs(const Tensor& logits,
   return {chosen_lp, top_lp, top_ids};
 }
 
+// ------------------------------------------------------- kv_copy_blocks_
+// cache[l, dst[p]] = cache[l, src[p]] for every layer, K and V, in one
+// launch on raw bytes (any 1/2/4-byte element).  src/dst VALUES are
+// trusted (as slot_mapping is): dst unique and disjoint from src.
+void kv_copy_blocks_(Tensor k_cache, Tensor v_cache, const Tensor& src,
+                     const Tensor& dst) {
+  TORCH_CHECK(k_cache.dim() == 5 && k_cache.sizes() == v_cache.sizes(),
+              "k/v cache must both be [L, NB, H, bs, D]");
+  TORCH_CHECK(k_cache.scalar_type() == v_cache.scalar_type(),
+              "k/v cache dtype mismatch");
+  TORCH_CHECK(k_cache.is_contiguous() && v_cache.is_contiguous(),
+              "k/v cache must be contiguous");
+  TORCH_CHECK(k_cache.is_cuda() && v_cache.device() == k_cache.device(),
+              "k/v cache must be on the same GPU");
+  const int64_t elt = k_cache.element_size();
+  TORCH_CHECK(elt == 1 || elt == 2 || elt == 4,
+              "kv cache element size must be 1, 2 or 4 bytes, got ", elt);
+  for (const Tensor* t : {&src, &dst}) {
+    TORCH_CHECK(t->scalar_type() == at::kInt && t->is_contiguous() &&
+                t->dim() == 1 && t->device() == k_cache.device(),
+                "src/dst must be contiguous 1-D int32 on the cache's device");
+  }
+  TORCH_CHECK(src.numel() == dst.numel(), "src/dst length mismatch");
+  const int64_t n_pairs = src.numel();
+  const int64_t n_layers = k_cache.size(0);
+  const int64_t chunk_bytes =
+      k_cache.size(2) * k_cache.size(3) * k_cache.size(4) * elt;
+  TORCH_CHECK(chunk_bytes % 16 == 0,
+              "a (layer, block) chunk must be a multiple of 16 bytes, got ",
+              chunk_bytes);
+  TORCH_CHECK(n_pairs <= 65535 && 2 * n_layers <= 65535,
+              "too many pairs/layers for one launch");
+  if (n_pairs == 0) return;
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(k_cache.device());
+  rlli::launch_kv_copy_blocks(k_cache.data_ptr(), v_cache.data_ptr(),
+                              src.data_ptr<int32_t>(),
+                              dst.data_ptr<int32_t>(), int(n_pairs),
+                              int(n_layers), k_cache.size(1), chunk_bytes,
+                              current_stream(k_cache));
+  check_launch("kv_copy_blocks_");
+}
+
 }  // namespace
 
 TORCH_LIBRARY(rlli, m) {
@@ -749,6 +791,8 @@ TORCH_LIBRARY(rlli, m) {
         "Tensor chunk_row0, Tensor chunk_pos0, Tensor chunk_nrows, "
         "Tensor chunk_btrow, Tensor block_tables, float scale, int n_q) "
         "-> Tensor");
+  m.def("kv_copy_blocks_(Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor src, "
+        "Tensor dst) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(rlli, CUDA, m) {
@@ -773,4 +817,5 @@ TORCH_LIBRARY_IMPL(rlli, CUDA, m) {
   m.impl("skinny2_silu_linear", &skinny2_silu_linear);
   m.impl("stream_probe", &stream_probe);
   m.impl("prefill_paged_attn", &prefill_paged_attn);
+  m.impl("kv_copy_blocks_", &kv_copy_blocks_);
 }

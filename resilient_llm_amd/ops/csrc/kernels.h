@@ -180,4 +180,14 @@ void launch_token_logprobs(
     uint64_t* cand,                    // [n_rows, n_split, k] workspace
     int n_split, hipStream_t stream);
 
+// Paged-cache block copy for forked sequences: for every layer l and pair
+// p, cache[l, dst[p]] = cache[l, src[p]] for K and V in one launch, as
+// raw bytes (chunk_bytes = H*bs*D*elt, a multiple of 16).  dst ids are
+// unique and disjoint from src ids (src may repeat); ids are not
+// validated on the device (kv_copy.hip).
+void launch_kv_copy_blocks(void* k_cache, void* v_cache, const int32_t* src,
+                           const int32_t* dst, int n_pairs, int n_layers,
+                           int64_t num_blocks, int64_t chunk_bytes,
+                           hipStream_t stream);
+
 }  // namespace rlli

@@ -235,6 +235,24 @@ def token_logprobs(logits: torch.Tensor, rows: torch.Tensor,
     return chosen, vals[:, :k].contiguous(), ids[:, :k].to(torch.int32)
 
 
+def kv_copy_blocks_(k_cache: torch.Tensor, v_cache: torch.Tensor,
+                    src: torch.Tensor, dst: torch.Tensor) -> None:
+    """In place, bit-exact: cache[l, dst[p]] = cache[l, src[p]] for every
+    layer l and pair p, for both [L, NB, H, bs, D] caches.  Works on the
+    raw bytes, so any element type (bf16, fp8, fp32) copies alike.  ``src``
+    may repeat; ``dst`` entries are unique and disjoint from ``src``."""
+    if src.numel() != dst.numel():
+        raise ValueError("src/dst length mismatch")
+    if src.numel() == 0:
+        return
+    s, d = src.long(), dst.long()
+    for cache in (k_cache, v_cache):
+        if cache.dim() != 5 or not cache.is_contiguous():
+            raise ValueError("cache must be contiguous [L, NB, H, bs, D]")
+        raw = cache.view(torch.uint8)
+        raw[:, d] = raw[:, s]
+
+
 # ---- fp8-activation emitters (quantized-weight GEMM path) ----
 def quantize_fp8_rowwise(t: torch.Tensor):
     """Per-row fp8-e4m3 quantization: (q, scales) with q*scales ~= t."""

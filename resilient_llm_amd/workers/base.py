@@ -14,6 +14,7 @@ Bedrock's ThrottlingException vs other failures (demo_cris.py:261-283).
 
 from __future__ import annotations
 
+import asyncio
 import dataclasses
 import random
 import time
@@ -93,6 +94,22 @@ class Worker:
 
     async def generate(self, req: GenerationRequest) -> GenerationResult:
         raise NotImplementedError
+
+    async def generate_n(self, reqs: list) -> list:
+        """OpenAI ``n``: the choices of ONE request — same prompt, one
+        GenerationRequest per choice (own request_id and seed) — as a
+        list of GenerationResult in order.  This default runs them as
+        concurrent ``generate`` calls and cancels the rest on the first
+        failure, so every worker supports ``n``; a worker that can share
+        the prompt's work between the choices overrides it."""
+        tasks = [asyncio.ensure_future(self.generate(r)) for r in reqs]
+        try:
+            return list(await asyncio.gather(*tasks))
+        except BaseException:
+            for t in tasks:
+                t.cancel()
+            await asyncio.gather(*tasks, return_exceptions=True)
+            raise
 
     def generate_stream(self, req: GenerationRequest) -> AsyncIterator[GenerationChunk]:
         raise NotImplementedError

@@ -152,6 +152,9 @@ class EngineWorker(Worker):
         # buffer engine-side, ONE queue item at finish (64x fewer loop
         # wakeups for non-streaming traffic)
         self._sinks: dict[str, list] = {}
+        # engine rids of n > 1 group members (generate_n): not offered
+        # for live migration
+        self._group_rids: set[str] = set()
         # live migration: adopted-but-unattached requests (gateway
         # request_id -> {"rid", "pre", "prompt_len", "buf", "done"});
         # outputs produced before the client re-attaches buffer here
@@ -171,6 +174,8 @@ class EngineWorker(Worker):
         # moved for RLLI_STEP_WATCHDOG_S, dump every thread's stack to
         # stderr ONCE — turns a silent GPU/thread wedge into a
         # diagnosable trace (ops feature; cheap: one counter compare/s)
+        self._wd_wake = threading.Event()
+        self._wd_thread = None
         wd_s = float(os.environ.get("RLLI_STEP_WATCHDOG_S", "60"))
         if wd_s > 0 and (tp_control is None or tp_control.is_leader):
             def _watchdog():
@@ -179,8 +184,10 @@ class EngineWorker(Worker):
                 last = -1
                 stuck_since = None
                 dumped = False
-                while not self._stop:
-                    time.sleep(1.0)
+                # wakes at once on close(): a daemon thread still asleep
+                # here when the interpreter finalizes can abort the
+                # process at exit
+                while not self._wd_wake.wait(1.0):
                     sc = self.engine.step_count
                     if not self.engine.has_work():
                         stuck_since = None
@@ -201,8 +208,10 @@ class EngineWorker(Worker):
                         faulthandler.dump_traceback(file=_sys.stderr)
                         dumped = True
                     last = sc
-            threading.Thread(target=_watchdog, daemon=True,
-                             name=f"watchdog-{self.device}").start()
+            self._wd_thread = threading.Thread(
+                target=_watchdog, daemon=True,
+                name=f"watchdog-{self.device}")
+            self._wd_thread.start()
 
     # --------------------------------------------------------- engine loop
     # TP lockstep heartbeat: followers BLOCK inside the control-group
@@ -281,27 +290,30 @@ class EngineWorker(Worker):
         if self.fault_mode == "error":
             raise WorkerError(f"{self.device} injected fault: error")
 
-    def _enqueue(self, req: GenerationRequest,
-                 mode: str = "stream") -> tuple[str, asyncio.Queue, int]:
-        self._check_fault()
-        prompt_ids = self.tokenizer.encode(render_prompt(req.messages))
+    def _params_of(self, req: GenerationRequest) -> SamplingParams:
         # a bias id past the serving model's vocab names no token of it:
         # biasing it is a no-op, not a worker failure (which would put
         # the worker in cooldown and fail the request over)
         vocab = getattr(self.engine.model.config, "vocab_size", None)
         logit_bias = [[int(t), float(b)] for t, b in req.logit_bias or ()
                       if not vocab or int(t) < vocab] or None
-        params = SamplingParams(max_tokens=req.max_tokens,
-                                temperature=req.temperature,
-                                top_p=req.top_p,
-                                presence_penalty=req.presence_penalty,
-                                frequency_penalty=req.frequency_penalty,
-                                seed=req.seed,
-                                logprobs=req.logprobs,
-                                top_logprobs=req.top_logprobs,
-                                logit_bias=logit_bias,
-                                top_k=req.top_k,
-                                min_p=req.min_p)
+        return SamplingParams(max_tokens=req.max_tokens,
+                              temperature=req.temperature,
+                              top_p=req.top_p,
+                              presence_penalty=req.presence_penalty,
+                              frequency_penalty=req.frequency_penalty,
+                              seed=req.seed,
+                              logprobs=req.logprobs,
+                              top_logprobs=req.top_logprobs,
+                              logit_bias=logit_bias,
+                              top_k=req.top_k,
+                              min_p=req.min_p)
+
+    def _enqueue(self, req: GenerationRequest,
+                 mode: str = "stream") -> tuple[str, asyncio.Queue, int]:
+        self._check_fault()
+        prompt_ids = self.tokenizer.encode(render_prompt(req.messages))
+        params = self._params_of(req)
         self._req_counter += 1
         rid = f"{req.request_id}-{self._req_counter}"
         q: asyncio.Queue = asyncio.Queue()
@@ -331,6 +343,58 @@ class EngineWorker(Worker):
         self._work_event.set()
         return rid, q, len(prompt_ids)
 
+    def _enqueue_group(self, reqs: list) -> tuple[list, list, int]:
+        """n choices of one request: tokenise once, one sink per member,
+        ONE add_request_group (the engine prefills the prompt once and
+        forks the members off it).  Returns (rids, queues, n_prompt)."""
+        self._check_fault()
+        prompt_ids = self.tokenizer.encode(render_prompt(reqs[0].messages))
+        params_list = [self._params_of(r) for r in reqs]
+        loop = asyncio.get_running_loop()
+        rids, queues = [], []
+        for r in reqs:
+            self._req_counter += 1
+            rids.append(f"{r.request_id}-{self._req_counter}")
+            queues.append(asyncio.Queue())
+        for rid, q in zip(rids, queues):
+            self._sinks[rid] = [q, loop, "final", [], None]
+        self._group_rids.update(rids)
+        try:
+            if self.tp_control is not None:
+                # leader: validate locally, then lockstep-broadcast the op
+                # with every member's full params
+                eng = self.engine
+                bs = eng.block_size
+                F = len(prompt_ids) // bs
+                blocks = sum(-(-(len(prompt_ids) + p.max_tokens) // bs)
+                             - (F if i else 0)
+                             for i, p in enumerate(params_list))
+                if len(reqs) > eng.max_batch_size:
+                    raise CapacityExceeded(
+                        f"n = {len(reqs)} exceeds max_batch_size "
+                        f"{eng.max_batch_size}")
+                if blocks > eng.kv.num_blocks:
+                    raise CapacityExceeded(
+                        f"group needs {blocks} KV blocks, cache has "
+                        f"{eng.kv.num_blocks}")
+                if len(eng.waiting) + eng._waiting_attached + len(reqs) \
+                        > eng.max_queue:
+                    raise CapacityExceeded(f"queue full ({eng.max_queue})")
+                self.tp_control.submit(
+                    ("add_group", rids, prompt_ids,
+                     [dataclasses.asdict(p) for p in params_list]))
+            else:
+                self.engine.add_request_group(rids, prompt_ids, params_list)
+        except BaseException as e:
+            for rid in rids:
+                self._sinks.pop(rid, None)
+            self._group_rids.difference_update(rids)
+            if isinstance(e, CapacityExceeded):
+                raise WorkerThrottled(str(e)) from e
+            raise
+        self._work_event.set()
+        return rids, queues, len(prompt_ids)
+
     # ------------------------------------------------------------ logprobs
     def _lp_token(self, token_id: int, logprob: float) -> dict:
         text = self.tokenizer.decode([token_id])
@@ -346,6 +410,7 @@ class EngineWorker(Worker):
 
     def _cleanup(self, rid: str) -> None:
         self._sinks.pop(rid, None)
+        self._group_rids.discard(rid)
 
     @property
     def in_flight(self) -> int:
@@ -371,8 +436,10 @@ class EngineWorker(Worker):
     def list_requests(self) -> list:
         """Gateway-side request ids of everything live on this worker
         (attached sinks + adopted-unattached) — the evacuation list for
-        drain-with-migration."""
-        ids = {rid.rsplit("-", 1)[0] for rid in self._sinks}
+        drain-with-migration.  Members of an n > 1 group are not offered:
+        a drain lets them finish, or the gateway replays the group."""
+        ids = {rid.rsplit("-", 1)[0] for rid in list(self._sinks)
+               if rid not in self._group_rids}
         with self._adopt_lock:
             ids |= set(self._adopted)
         return sorted(ids)
@@ -387,6 +454,9 @@ class EngineWorker(Worker):
         rid = self._find_rid(request_id)
         if rid is None:
             raise WorkerError(f"no live request {request_id!r}")
+        if rid in self._group_rids:
+            raise WorkerError(f"request {request_id!r} is one of n > 1 "
+                              "choices: groups are not live-migrated")
         self.engine.request_extract(rid)
         self._work_event.set()
         state = None
@@ -553,35 +623,75 @@ class EngineWorker(Worker):
                 raise WorkerError(f"engine error: {got}") from got
             outs, first_t = got
             finished = True    # engine freed the sequence itself: no abort
-            token_ids = pre + [o.token_id for o in outs]
-            finish = outs[-1].finish_reason or "stop"
-            text = self.tokenizer.decode(token_ids)
-            cut = _earliest_stop(text, req.stop)
-            if cut >= 0:
-                text = text[:cut]
-                finish = "stop"
-            self.total_served += 1
-            entries = None
-            if req.logprobs:
-                # one entry per counted completion token: a stop-sequence
-                # cut shortens the text, not the token count or this list
-                entries = [self._lp_entry(t, r[0], r[1])
-                           for t, r in zip(pre, pre_lp)]
-                entries += [self._lp_entry(o.token_id, o.logprob,
-                                           o.top_logprobs)
-                            for o in outs if o.logprob is not None]
-            return GenerationResult(
-                text=text,
-                prompt_tokens=n_prompt,
-                completion_tokens=len(token_ids),
-                finish_reason=finish,
-                ttft_ms=max(0.0, (first_t - t0) * 1000.0),
-                logprobs=entries)
+            return self._result_of(req, outs, first_t, t0, n_prompt, pre,
+                                   pre_lp)
         finally:
             self._in_flight -= 1
             self._cleanup(rid)
             if not finished:   # abort only requests the engine still owns
                 self._abort(rid)
+
+    def _result_of(self, req: GenerationRequest, outs: list, first_t: float,
+                   t0: float, n_prompt: int, pre: list,
+                   pre_lp: list) -> GenerationResult:
+        """The GenerationResult of one finished request from its engine
+        outputs: stop-sequence cut, logprob entries, ttft."""
+        token_ids = pre + [o.token_id for o in outs]
+        finish = outs[-1].finish_reason or "stop"
+        text = self.tokenizer.decode(token_ids)
+        cut = _earliest_stop(text, req.stop)
+        if cut >= 0:
+            text = text[:cut]
+            finish = "stop"
+        self.total_served += 1
+        entries = None
+        if req.logprobs:
+            # one entry per counted completion token: a stop-sequence
+            # cut shortens the text, not the token count or this list
+            entries = [self._lp_entry(t, r[0], r[1])
+                       for t, r in zip(pre, pre_lp)]
+            entries += [self._lp_entry(o.token_id, o.logprob,
+                                       o.top_logprobs)
+                        for o in outs if o.logprob is not None]
+        return GenerationResult(
+            text=text,
+            prompt_tokens=n_prompt,
+            completion_tokens=len(token_ids),
+            finish_reason=finish,
+            ttft_ms=max(0.0, (first_t - t0) * 1000.0),
+            logprobs=entries)
+
+    async def generate_n(self, reqs: list) -> list:
+        """The n choices of one request through ONE add_request_group:
+        the prompt is tokenised and prefilled once and the choices fork
+        off it (shared prompt blocks, a private tail each).  Any failure
+        aborts every member."""
+        if len(reqs) == 1:
+            return [await self.generate(reqs[0])]
+        t0 = time.monotonic()
+        rids, queues, n_prompt = self._enqueue_group(reqs)
+        self._in_flight += len(reqs)
+        done = [False] * len(reqs)
+        try:
+            results = []
+            for i, (req, q) in enumerate(zip(reqs, queues)):
+                got = await q.get()
+                self._check_fault()
+                if isinstance(got, WorkerError):
+                    raise got
+                if isinstance(got, Exception):
+                    raise WorkerError(f"engine error: {got}") from got
+                outs, first_t = got
+                done[i] = True
+                results.append(self._result_of(req, outs, first_t, t0,
+                                               n_prompt, [], []))
+            return results
+        finally:
+            self._in_flight -= len(reqs)
+            for rid, fin in zip(rids, done):
+                self._cleanup(rid)
+                if not fin:            # the engine still owns this member
+                    self._abort(rid)
 
     async def _stream_impl(self, req: GenerationRequest) -> AsyncIterator[GenerationChunk]:
         attached = self._attach(req, mode="stream")
@@ -686,4 +796,7 @@ class EngineWorker(Worker):
     async def close(self) -> None:
         self._stop = True
         self._work_event.set()
+        self._wd_wake.set()
         self._thread.join(timeout=5)
+        if self._wd_thread is not None:
+            self._wd_thread.join(timeout=5)

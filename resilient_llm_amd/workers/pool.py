@@ -59,6 +59,13 @@ class TPControl:
                 if kind == "add":
                     _, rid, prompt_ids, params = op
                     engine.add_request(rid, prompt_ids, SamplingParams(**params))
+                elif kind == "add_group":
+                    # n > 1 choices of one prompt: every member's full
+                    # params ride the broadcast
+                    _, rids, prompt_ids, params_list = op
+                    engine.add_request_group(
+                        rids, prompt_ids,
+                        [SamplingParams(**p) for p in params_list])
                 elif kind == "abort":
                     engine.abort(op[1])
             except Exception:

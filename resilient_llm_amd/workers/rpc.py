@@ -98,6 +98,12 @@ class WorkerRpcServer:
                 res = await self.worker.generate(req)
                 await reply({"id": mid, "type": "result",
                              "data": dataclasses.asdict(res)})
+            elif op == "generate_n":
+                reqs = [GenerationRequest(**d) for d in data["reqs"]]
+                results = await self.worker.generate_n(reqs)
+                await reply({"id": mid, "type": "result",
+                             "data": {"results": [dataclasses.asdict(r)
+                                                  for r in results]}})
             elif op == "stream":
                 req = GenerationRequest(**data)
                 async for chunk in self.worker.generate_stream(req):
@@ -249,6 +255,23 @@ class RpcWorkerClient(Worker):
             return GenerationResult(**msg["data"])
         finally:
             self._in_flight -= 1
+            if mid is not None:
+                self._queues.pop(mid, None)
+
+    async def generate_n(self, reqs: list) -> list:
+        """The n choices of one request in ONE frame, so the remote
+        worker can fork them off a single prefill."""
+        self._in_flight += len(reqs)
+        mid = None
+        try:
+            mid, q = await self._call(
+                "generate_n", {"reqs": [dataclasses.asdict(r) for r in reqs]})
+            msg = await q.get()
+            if msg["type"] == "error":
+                _raise_remote(msg["data"])
+            return [GenerationResult(**d) for d in msg["data"]["results"]]
+        finally:
+            self._in_flight -= len(reqs)
             if mid is not None:
                 self._queues.pop(mid, None)
 
