@@ -122,6 +122,15 @@ class Config:
     cris_model: Optional[str] = None      # alias spread across all GPUs (X10)
     raw: dict = dataclasses.field(default_factory=dict)
 
+    def worker_adapters(self, kind: str, target: str) -> dict:
+        """LoRA adapters {name: path} of one worker: the union of the
+        ``adapters`` maps of every deployment pinned to it."""
+        out: dict = {}
+        for d in self.deployments:
+            if d.backend_kind == kind and d.backend_target == target:
+                out.update(d.params.get("adapters") or {})
+        return out
+
     def deployments_for(self, alias: str) -> list[Deployment]:
         return [d for d in self.deployments if d.model_name == alias]
 
@@ -176,6 +185,19 @@ def _parse_deployment(entry: Any, idx: int) -> Deployment:
                  and 0 <= extra["spec_lookup"] <= 16,
                  f"model_list[{idx}].litellm_params.spec_lookup must be "
                  f"an int in [0, 16], got {extra['spec_lookup']!r}")
+    # LoRA: ``adapters`` {name: PEFT directory} loads on the worker at
+    # start, ``adapter`` names the one this deployment serves
+    if "adapters" in extra:
+        ad = extra["adapters"]
+        _require(isinstance(ad, dict) and bool(ad) and all(
+            isinstance(k, str) and k and isinstance(v, str) and v
+            and "=" not in k for k, v in ad.items()),
+            f"model_list[{idx}].litellm_params.adapters must be a "
+            f"non-empty mapping name -> path, got {ad!r}")
+    if "adapter" in extra:
+        _require(isinstance(extra["adapter"], str) and bool(extra["adapter"]),
+                 f"model_list[{idx}].litellm_params.adapter must be a "
+                 f"name, got {extra['adapter']!r}")
     return Deployment(model_name=name, model=model, model_id=model_id,
                       rpm=rpm, tpm=tpm, weight=int(weight), params=extra)
 
@@ -263,6 +285,44 @@ def load_config(path: str | os.PathLike[str] | None = None,
             _require(d.backend_target in cluster.pools,
                      f"deployment {d.model_name}: pool {d.backend_target!r} "
                      f"not defined under cluster.pools")
+    # LoRA adapters are per worker: an alias may only serve an adapter
+    # its worker loads, and the worker must be one that can run them
+    for d in deployments:
+        if "adapter" not in d.params and "adapters" not in d.params:
+            continue
+        on_worker = [e for e in deployments
+                     if e.backend_kind == d.backend_kind
+                     and e.backend_target == d.backend_target]
+        loaded: dict = {}
+        for e in on_worker:
+            loaded.update(e.params.get("adapters") or {})
+        if "adapter" in d.params:
+            _require(d.backend_target != "*",
+                     f"deployment {d.model_name}: 'adapter' needs a pinned "
+                     f"worker, not the spread target {d.model!r}")
+            _require(d.params["adapter"] in loaded,
+                     f"deployment {d.model_name}: adapter "
+                     f"{d.params['adapter']!r} is not in the adapters of "
+                     f"{d.backend_kind}/{d.backend_target} "
+                     f"({sorted(loaded) or 'none'})")
+        if loaded:
+            _require(not any(e.params.get("quantization") == "fp8"
+                             for e in on_worker),
+                     f"deployment {d.model_name}: adapters cannot be "
+                     f"combined with quantization: fp8 on "
+                     f"{d.backend_kind}/{d.backend_target} (the fp8 path "
+                     f"hands the MLP fp8 activations)")
+            if d.backend_kind == "pool":
+                _require(cluster.pools[d.backend_target].tensor_parallel == 1,
+                         f"deployment {d.model_name}: adapters are not "
+                         f"supported on pool {d.backend_target!r} with "
+                         f"tensor_parallel > 1")
+                # a TP = 1 pool still runs the lockstep op stream, which
+                # does not carry the adapter: gpu/ workers serve adapters
+                _require(False,
+                         f"deployment {d.model_name}: adapters are served "
+                         f"by gpu/<device> workers only, not by pool "
+                         f"{d.backend_target!r}")
     # every fallback target must be a known alias
     known = {d.model_name for d in deployments}
     for alias, targets in router.fallbacks.items():

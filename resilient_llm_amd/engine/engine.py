@@ -109,6 +109,9 @@ class SeqState:
     # group leader aborted before the fork: keeps prefilling for its
     # children, emits nothing and is freed at the fork
     silent: bool = False
+    # LoRA adapter (a name loaded on the model) this sequence runs under;
+    # None = the base weights
+    adapter: Optional[str] = None
 
     def blocks_needed(self, block_size: int) -> int:
         return -(-(len(self.prompt_ids) + self.params.max_tokens) // block_size)
@@ -231,11 +234,14 @@ class LLMEngine:
                     or self._pending or self._adopt_queue
                     or self._extract_reqs)
 
-    def _validate(self, prompt_ids: list,
-                  params: SamplingParams) -> SamplingParams:
+    def _validate(self, prompt_ids: list, params: SamplingParams,
+                  adapter: Optional[str] = None) -> SamplingParams:
         """The API-boundary checks every admitted sequence passes
         (add_request and each member of add_request_group); returns the
         params, with logit_bias normalised to ascending ids."""
+        if adapter is not None and adapter not in getattr(
+                self.model, "adapter_names", ()):
+            raise ValueError(f"unknown adapter {adapter!r}")
         if not 0 <= params.top_logprobs <= 20:
             raise ValueError(
                 f"top_logprobs must be in 0..20, got {params.top_logprobs}")
@@ -272,17 +278,40 @@ class LLMEngine:
                     f"min={lo} max={hi}")
         return params
 
+    @staticmethod
+    def _prefix_salt(adapter: Optional[str]) -> bytes:
+        """Prefix-cache salt: KV computed under an adapter is not the
+        base model's KV, so its block keys live in a chain of their own."""
+        return b"" if adapter is None else b"adapter:" + adapter.encode()
+
+    def _adapter_idx(self, adapters: list) -> Optional[torch.Tensor]:
+        """Per-row adapter names -> the int32 stack-index tensor the
+        model takes (-1 = none), or None — touching no device state —
+        when no row has an adapter.  A host->device upload: call it only
+        where the host already waits (batch rebuild, mixed step)."""
+        if not any(a is not None for a in adapters):
+            return None
+        index = {None: -1}
+        for a in set(adapters) - {None}:
+            index[a] = self.model.adapter_index(a)
+        return torch.tensor([index[a] for a in adapters], dtype=torch.int32,
+                            device=self.device)
+
     def add_request(self, req_id: str, prompt_ids: list,
-                    params: Optional[SamplingParams] = None) -> None:
-        params = self._validate(prompt_ids, params or SamplingParams())
+                    params: Optional[SamplingParams] = None,
+                    adapter: Optional[str] = None) -> None:
+        params = self._validate(prompt_ids, params or SamplingParams(),
+                                adapter)
         if len(self.waiting) + self._waiting_attached >= self.max_queue:
             raise CapacityExceeded(f"queue full ({self.max_queue})")
-        seq = SeqState(req_id=req_id, prompt_ids=list(prompt_ids), params=params)
+        seq = SeqState(req_id=req_id, prompt_ids=list(prompt_ids),
+                       params=params, adapter=adapter)
         self._arrival_counter += 1
         seq.default_seed = (self.seed * 1000003
                             + self._arrival_counter) & 0x7fffffffffffffff
         if self.enable_prefix_caching:
-            seq.block_keys = block_hash_chain(seq.prompt_ids, self.block_size)
+            seq.block_keys = block_hash_chain(seq.prompt_ids, self.block_size,
+                                              self._prefix_salt(adapter))
         if len(seq.prompt_ids) + params.max_tokens > self.max_model_len:
             raise CapacityExceeded(
                 f"prompt+max_tokens = "
@@ -297,7 +326,8 @@ class LLMEngine:
             self._live.add(req_id)
 
     def add_request_group(self, req_ids: list, prompt_ids: list,
-                          params_list: list) -> None:
+                          params_list: list,
+                          adapter: Optional[str] = None) -> None:
         """Admit ONE prompt with n = len(req_ids) continuations (OpenAI
         ``n``), each with its own SamplingParams and reported under its
         own req_id.  Member 0 (the leader) prefills the prompt once; in
@@ -305,12 +335,14 @@ class LLMEngine:
         share its full prompt blocks by refcount, get a private copy of
         the partial last block, and sample their first token from the
         leader's last-row logits with their own params and seed.  From
-        there every member is an ordinary sequence."""
+        there every member is an ordinary sequence.  ``adapter`` is the
+        whole group's: the shared prompt KV is computed under it."""
         n = len(req_ids)
         if n < 1 or len(params_list) != n or len(set(req_ids)) != n:
             raise ValueError("add_request_group needs n >= 1 distinct "
                              "req_ids and one SamplingParams per member")
-        params_list = [self._validate(prompt_ids, p or SamplingParams())
+        params_list = [self._validate(prompt_ids, p or SamplingParams(),
+                                      adapter)
                        for p in params_list]
         if n > self.max_batch_size:
             raise CapacityExceeded(
@@ -322,7 +354,7 @@ class LLMEngine:
         total_blocks = 0
         for i, (rid, params) in enumerate(zip(req_ids, params_list)):
             seq = SeqState(req_id=rid, prompt_ids=list(prompt_ids),
-                           params=params)
+                           params=params, adapter=adapter)
             if len(seq.prompt_ids) + params.max_tokens > self.max_model_len:
                 raise CapacityExceeded(
                     f"prompt+max_tokens = "
@@ -343,7 +375,8 @@ class LLMEngine:
         leader.children = seqs[1:]
         if self.enable_prefix_caching:
             leader.block_keys = block_hash_chain(leader.prompt_ids,
-                                                 self.block_size)
+                                                 self.block_size,
+                                                 self._prefix_salt(adapter))
         with self._queue_lock:
             self.waiting.append(leader)
             self._live.update(req_ids)
@@ -664,6 +697,7 @@ class LLMEngine:
                              "output_logprobs": [],
                              "params": dataclasses.asdict(seq.params),
                              "default_seed": seq.default_seed,
+                             "adapter": seq.adapter,
                              "n_cached": 0,
                              "block_size": self.block_size,
                              "kv": None}
@@ -680,6 +714,7 @@ class LLMEngine:
                              "output_logprobs": list(seq.output_logprobs),
                              "params": dataclasses.asdict(seq.params),
                              "default_seed": seq.default_seed,
+                             "adapter": seq.adapter,
                              "n_cached": seq.n_cached,
                              "block_size": self.block_size,
                              "kv": None}
@@ -740,7 +775,16 @@ class LLMEngine:
             rid = state["rid"]
             try:
                 params = SamplingParams(**state["params"])
-                seq = SeqState(req_id=rid,
+                # absent in blobs from before adapters.  An adapter this
+                # engine has not loaded fails the adoption: continuing on
+                # the base weights would silently change the model
+                adapter = state.get("adapter")
+                if adapter is not None and adapter not in getattr(
+                        self.model, "adapter_names", ()):
+                    raise ValueError(
+                        f"cannot adopt {rid!r}: adapter {adapter!r} is not "
+                        "loaded on this engine")
+                seq = SeqState(req_id=rid, adapter=adapter,
                                prompt_ids=list(state["prompt_ids"]),
                                params=params,
                                output_ids=list(state["output_ids"]),
@@ -777,7 +821,8 @@ class LLMEngine:
                     seq.output_logprobs = []
                     if self.enable_prefix_caching:
                         seq.block_keys = block_hash_chain(
-                            seq.prompt_ids, self.block_size)
+                            seq.prompt_ids, self.block_size,
+                            self._prefix_salt(adapter))
                     with self._queue_lock:
                         self.waiting.append(seq)
                 with self._queue_lock:
@@ -991,6 +1036,7 @@ class LLMEngine:
         positions = [s.n_cached for s in seqs_d]
         slots = [self._slot(s, s.n_cached) for s in seqs_d]
         seq_lens_d = [s.n_cached + 1 for s in seqs_d]
+        adapters = [s.adapter for s in seqs_d]
 
         budget = self._prefill_budget
         chunk_plan: list = []
@@ -1019,6 +1065,7 @@ class LLMEngine:
             input_ids.extend(seq.prompt_ids[start:start + n])
             positions.extend(range(start, start + n))
             slots.extend(self._slot(seq, p) for p in range(start, start + n))
+            adapters.extend([seq.adapter] * n)
             if start + n == len(seq.prompt_ids):
                 sample_idx.append(row + n - 1)
                 sampled_seqs.append(seq)
@@ -1045,10 +1092,11 @@ class LLMEngine:
                 cu.append(cu[-1] + n)
             ids_t, pos_t, slots_t, cu_t = (i32(input_ids), i32(positions),
                                            i32(slots), i32(cu))
+            lora_kw = self._lora_kw(adapters)
             self.stats["prefill_prep_time"] += time.monotonic() - t_prep
             t_fwd = time.monotonic()
             logits = self.model.forward_prefill(ids_t, pos_t, self.kv,
-                                                slots_t, cu_t)
+                                                slots_t, cu_t, **lora_kw)
             self.stats["prefill_fwd_time"] += time.monotonic() - t_fwd
             return self._mixed_finish(chunk_plan, sampled_seqs, logits)
 
@@ -1058,12 +1106,20 @@ class LLMEngine:
                 i32(c_row0), i32(c_pos0), i32(c_nrows), i32(c_btrow),
                 bt_tensor(bt_rows),
                 torch.tensor(sample_idx, dtype=torch.long, device=dev))
+        lora_kw = self._lora_kw(adapters)
         self.stats["prefill_prep_time"] += time.monotonic() - t_prep
         t_fwd = time.monotonic()
-        logits = self.model.forward_mixed(*args)
+        logits = self.model.forward_mixed(*args, **lora_kw)
         self.stats["prefill_fwd_time"] += time.monotonic() - t_fwd
         return self._mixed_finish(chunk_plan, sampled_seqs, logits,
                                   decode_seqs=seqs_d)
+
+    def _lora_kw(self, adapters: list) -> dict:
+        """The forward's ``adapter_idx`` keyword for a step whose rows
+        carry these adapters — empty when none does, so an adapter-free
+        step calls the model exactly as before."""
+        idx = self._adapter_idx(adapters)
+        return {} if idx is None else {"adapter_idx": idx}
 
     def _fork_groups(self, sampled_seqs: list, logits: torch.Tensor):
         """Fork every n > 1 group whose leader's prompt completed in this
@@ -1203,9 +1259,11 @@ class LLMEngine:
         c_row0, c_pos0, c_nrows, c_btrow = [], [], [], []
         bt_rows: list[list] = []
         metas = []
+        adapters: list = []
         row = 0
         for s, prop in zip(seqs, proposals):
             toks = [s.output_ids[-1]] + prop
+            adapters.extend([s.adapter] * len(toks))
             btr = len(bt_rows)
             bt_rows.append(s.blocks)
             c_row0.append(row)
@@ -1233,7 +1291,8 @@ class LLMEngine:
             i32(input_ids), i32(positions), self.kv, i32(slots), 0,
             None, None, i32(c_row0), i32(c_pos0), i32(c_nrows), i32(c_btrow),
             bt_tensor(bt_rows),
-            torch.arange(row, dtype=torch.long, device=dev))
+            torch.arange(row, dtype=torch.long, device=dev),
+            **self._lora_kw(adapters))
         greedy = logits.argmax(-1).tolist()           # host sync (spec mode)
 
         outs: list[StepOutput] = []
@@ -1292,6 +1351,8 @@ class LLMEngine:
         self._b_lp_plan = self._lp_plan(seqs)
         # likewise the constrained rows and their static constraints
         self._b_cs_plan = self._cs_plan(seqs)
+        # per-row adapter indices (None when no row has an adapter)
+        self._b_lora_kw = self._lora_kw([s.adapter for s in seqs])
         self._batch_dirty = False
         self._graph_loaded = False
 
@@ -1300,7 +1361,10 @@ class LLMEngine:
         if getattr(self, "_batch_dirty", True) or self._b_ids.shape[0] != len(seqs):
             self._rebuild_batch()
         gr = self.graph_runner
-        if gr is not None and gr.steady_ok(len(seqs), self._b_bt.shape[1]):
+        # a batch with an adapter row takes the eager branch: the captured
+        # graph holds the base model's launches only
+        if (gr is not None and not self._b_lora_kw
+                and gr.steady_ok(len(seqs), self._b_bt.shape[1])):
             # steady path: the WHOLE step (slots, forward, sample, state
             # advance) is one graph replay; the static buffers are loaded
             # only when the batch composition changed (graph.py)
@@ -1336,8 +1400,8 @@ class LLMEngine:
             for seq in seqs:
                 seq.n_cached += 1      # KV of the fed token was appended
             return self._queue_pending(seqs, tok_dev, lp)
-        # eager path (no graphs, torch-side sampling, or out-of-envelope
-        # block tables)
+        # eager path (no graphs, torch-side sampling, out-of-envelope
+        # block tables, or a row under a LoRA adapter)
         pos = self._b_pos
         bt = self._b_bt
         block_idx = (pos // self.block_size).long()
@@ -1345,7 +1409,8 @@ class LLMEngine:
             * self.block_size + (pos - block_idx.int() * self.block_size)
         seq_lens = pos + 1
         logits = self.model.forward_decode(self._b_ids, pos, self.kv,
-                                           slots, bt, seq_lens)
+                                           slots, bt, seq_lens,
+                                           **self._b_lora_kw)
         if self._b_torch_sampling:
             tokens = self._sample(logits, seqs)     # torch top-p path (sync)
             tok_dev = torch.tensor(tokens, dtype=torch.int32,

@@ -28,10 +28,13 @@ class OutOfBlocks(RuntimeError):
     """KV budget exhausted — the worker surfaces this as Throttled (X13)."""
 
 
-def block_hash_chain(token_ids, block_size: int) -> list[bytes]:
-    """Content keys for each FULL block of a prompt: sha1(parent, tokens)."""
+def block_hash_chain(token_ids, block_size: int,
+                     salt: bytes = b"") -> list[bytes]:
+    """Content keys for each FULL block of a prompt: sha1(parent, tokens).
+    ``salt`` seeds the chain: prompts hashed under different salts (the
+    engine salts with the LoRA adapter's name) never share a key."""
     keys = []
-    parent = b"root"
+    parent = b"root" + salt
     for i in range(len(token_ids) // block_size):
         blk = token_ids[i * block_size:(i + 1) * block_size]
         h = hashlib.sha1(parent + struct.pack(f"<{block_size}i", *blk)).digest()

@@ -456,6 +456,9 @@ class GatewayApp:
             if body.get("logit_bias") else None,
             top_k=int(body.get("top_k") or 0),
             min_p=float(body.get("min_p") or 0.0),
+            # the deployment's LoRA adapter: several aliases may share one
+            # worker's base weights and differ only here
+            adapter=ticket.deployment.params.get("adapter"),
         )
 
     def _record(self, ticket: Ticket, greq: Optional[GenerationRequest],

@@ -154,6 +154,14 @@ class LlamaForCausalLM:
         self.kv_size = self.n_kv_heads * c.head_dim
         self.scale = 1.0 / math.sqrt(c.head_dim)
         self.params: dict[str, torch.Tensor] = {}
+        # per-request LoRA adapters (load_adapter): name -> stack index,
+        # the source tensors per adapter, and the stacked device tensors
+        # the batched kernels read (None until the first adapter loads)
+        self.adapter_names: list[str] = []
+        self._adapter_src: dict[str, dict] = {}
+        self.lora: Optional[dict] = None
+        self.lora_scale: Optional[torch.Tensor] = None
+        self.lora_slices: dict[str, list] = {}
         self._init_weights(seed)
         if self.quant == "fp8":
             self._quantize_weights()
@@ -330,6 +338,153 @@ class LlamaForCausalLM:
         st.save_file({k: v.contiguous().cpu() for k, v in out.items()},
                      os.path.join(path, "model.safetensors"))
 
+    # ----------------------------------------------------------- adapters
+    # HF/PEFT module -> (fused projection, slice within it)
+    _LORA_MODULES = {"q_proj": ("qkv", 0), "k_proj": ("qkv", 1),
+                     "v_proj": ("qkv", 2), "o_proj": ("o", 0),
+                     "gate_proj": ("gate_up", 0), "up_proj": ("gate_up", 1),
+                     "down_proj": ("down", 0)}
+    LORA_MAX_RANK = 64
+
+    def _lora_geometry(self) -> dict:
+        """Fused projection -> (input width K, [slice widths])."""
+        c = self.config
+        return {"qkv": (c.hidden_size, [self.q_size, self.kv_size,
+                                        self.kv_size]),
+                "o": (self.q_size, [c.hidden_size]),
+                "gate_up": (c.hidden_size, [self.inter, self.inter]),
+                "down": (self.inter, [c.hidden_size])}
+
+    @staticmethod
+    def _peft_key(i: int, module: str, which: str) -> str:
+        block = "mlp" if module in ("gate_proj", "up_proj", "down_proj") \
+            else "self_attn"
+        return (f"base_model.model.model.layers.{i}.{block}.{module}."
+                f"lora_{which}.weight")
+
+    def adapter_index(self, name: str) -> int:
+        return self.adapter_names.index(name)
+
+    def add_adapter(self, name: str, r: int, lora_alpha: float,
+                    target_modules, weights: dict) -> None:
+        """Register one LoRA adapter from PEFT-named tensors
+        (``...layers.{i}.self_attn.q_proj.lora_A.weight`` [r, in] and
+        ``lora_B.weight`` [out, r]) and rebuild the stacks.  q/k/v and
+        gate/up fold into the fused qkv and gate_up projections as rank
+        slices; a module the adapter does not target gets zero B.  A name
+        already loaded is replaced in place (same stack index)."""
+        if self.tp_world > 1:
+            raise RuntimeError("LoRA adapters are not supported with "
+                               "tensor_parallel > 1")
+        if self.quant is not None:
+            raise RuntimeError("LoRA adapters are not supported on a "
+                               "weight-quantized model")
+        r = int(r)
+        if not 1 <= r <= self.LORA_MAX_RANK:
+            raise ValueError(f"adapter {name!r}: r must be in 1.."
+                             f"{self.LORA_MAX_RANK}, got {r}")
+        targets = sorted(target_modules)
+        unknown = [m for m in targets if m not in self._LORA_MODULES]
+        if unknown:
+            raise ValueError(f"adapter {name!r}: unsupported "
+                             f"target_modules {unknown}")
+        geo = self._lora_geometry()
+        tensors: dict[str, torch.Tensor] = {}
+        for i in range(self.config.n_layers):
+            for m in targets:
+                proj, s = self._LORA_MODULES[m]
+                K, widths = geo[proj]
+                for which, shape in (("A", (r, K)), ("B", (widths[s], r))):
+                    key = self._peft_key(i, m, which)
+                    if key not in weights:
+                        raise KeyError(f"adapter {name!r}: missing {key}")
+                    t = weights[key]
+                    if tuple(t.shape) != shape:
+                        raise ValueError(
+                            f"adapter {name!r}: {key} has shape "
+                            f"{tuple(t.shape)}, expected {shape}")
+                    tensors[key] = t.to(self.dtype).contiguous().cpu()
+        self._adapter_src[name] = {"r": r, "lora_alpha": float(lora_alpha),
+                                   "target_modules": targets,
+                                   "tensors": tensors}
+        if name not in self.adapter_names:
+            self.adapter_names.append(name)
+        self._rebuild_adapter_stack()
+
+    def _rebuild_adapter_stack(self) -> None:
+        """Stack every loaded adapter per fused projection: A
+        [n, n_slices * r_max, K] and B [n, O, r_max], zero-padded to the
+        largest rank loaded.  Runs on load, never on a hot path."""
+        n = len(self.adapter_names)
+        srcs = [self._adapter_src[a] for a in self.adapter_names]
+        r_max = max(s["r"] for s in srcs)
+        geo = self._lora_geometry()
+        lora: dict[str, tuple] = {}
+        for proj, (K, widths) in geo.items():
+            ends, lo = [], 0
+            for w in widths:
+                lo += w
+                ends.append(lo)
+            self.lora_slices[proj] = ends
+        for i in range(self.config.n_layers):
+            for proj, (K, widths) in geo.items():
+                A = torch.zeros((n, len(widths) * r_max, K), dtype=self.dtype)
+                B = torch.zeros((n, sum(widths), r_max), dtype=self.dtype)
+                for ai, src in enumerate(srcs):
+                    r = src["r"]
+                    for m in src["target_modules"]:
+                        mproj, s = self._LORA_MODULES[m]
+                        if mproj != proj:
+                            continue
+                        lo = sum(widths[:s])
+                        A[ai, s * r_max:s * r_max + r] = \
+                            src["tensors"][self._peft_key(i, m, "A")]
+                        B[ai, lo:lo + widths[s], :r] = \
+                            src["tensors"][self._peft_key(i, m, "B")]
+                lora[f"l{i}.{proj}"] = (A.to(self.device), B.to(self.device))
+        self.lora = lora
+        self.lora_scale = torch.tensor(
+            [s["lora_alpha"] / s["r"] for s in srcs], dtype=torch.float32,
+            device=self.device)
+
+    def load_adapter(self, name: str, path: str) -> None:
+        """Load a PEFT LoRA directory: ``adapter_config.json`` (r,
+        lora_alpha, target_modules) + ``adapter_model.safetensors``."""
+        import json
+        import safetensors.torch as st
+        with open(os.path.join(path, "adapter_config.json")) as f:
+            cfg = json.load(f)
+        weights = st.load_file(os.path.join(path,
+                                            "adapter_model.safetensors"))
+        self.add_adapter(name, cfg["r"], cfg["lora_alpha"],
+                         cfg["target_modules"], weights)
+
+    def save_adapter(self, name: str, path: str) -> str:
+        """Write a loaded adapter back as a PEFT directory — the
+        round-trip fixture for the adapter tests.  Returns ``path``."""
+        import json
+        import safetensors.torch as st
+        src = self._adapter_src[name]
+        os.makedirs(path, exist_ok=True)
+        with open(os.path.join(path, "adapter_config.json"), "w") as f:
+            json.dump({"peft_type": "LORA", "r": src["r"],
+                       "lora_alpha": src["lora_alpha"],
+                       "target_modules": src["target_modules"]}, f)
+        st.save_file(dict(src["tensors"]),
+                     os.path.join(path, "adapter_model.safetensors"))
+        return path
+
+    def _lora_add_(self, key: str, proj: str, x: torch.Tensor,
+                   out: torch.Tensor, adapter_idx: torch.Tensor) -> torch.Tensor:
+        """out += the per-row low-rank update of projection ``key``, next
+        to (after) its base GEMM: one shrink and one expand launch."""
+        if self.lora is None:
+            raise RuntimeError("adapter_idx given but no adapter is loaded")
+        A, B = self.lora[key]
+        y = ops.lora_shrink(x.contiguous(), A, adapter_idx)
+        return ops.lora_expand_add_(out, y, B, self.lora_scale,
+                                    self.lora_slices[proj], adapter_idx)
+
     def param_bytes(self) -> int:
         seen = set()
         total = 0
@@ -348,9 +503,17 @@ class LlamaForCausalLM:
 
     def _layer(self, i: int, x: torch.Tensor, residual: Optional[torch.Tensor],
                positions: torch.Tensor, kv_cache, slot_mapping: torch.Tensor,
-               attn_fn) -> tuple[torch.Tensor, torch.Tensor]:
+               attn_fn, adapter_idx: Optional[torch.Tensor] = None
+               ) -> tuple[torch.Tensor, torch.Tensor]:
+        """``adapter_idx`` ([T] int32, -1 = none): per-row LoRA adapter;
+        each of the four projections is then followed by a shrink and an
+        expand on its output (o and down: before the all-reduce and the
+        residual).  None executes nothing new."""
         p = self.params
         c = self.config
+        if adapter_idx is not None:
+            return self._layer_lora(i, x, residual, kv_cache, attn_fn,
+                                    adapter_idx)
         if residual is None:
             residual = x.clone()
             h = ops.rmsnorm(x, p[f"l{i}.ln1"], c.rms_eps)
@@ -374,9 +537,40 @@ class LlamaForCausalLM:
         mlp = self._all_reduce(_linear(ops.silu_mul(gu), p[f"l{i}.down"]))
         return mlp, residual
 
+    def _layer_lora(self, i: int, x: torch.Tensor,
+                    residual: Optional[torch.Tensor], kv_cache, attn_fn,
+                    adapter_idx: torch.Tensor
+                    ) -> tuple[torch.Tensor, torch.Tensor]:
+        """``_layer`` with the low-rank update after every projection
+        (bf16 weights only: adapters do not load on a quantized model)."""
+        p = self.params
+        c = self.config
+        if residual is None:
+            residual = x.clone()
+            h = ops.rmsnorm(x, p[f"l{i}.ln1"], c.rms_eps)
+        else:
+            h = ops.rmsnorm_residual_(x, residual, p[f"l{i}.ln1"], c.rms_eps)
+        qkv = self._lora_add_(f"l{i}.qkv", "qkv", h,
+                              _linear(h, p[f"l{i}.qkv"]), adapter_idx)
+        k_cache, v_cache = kv_cache.layer(i)
+        attn_out = attn_fn(i, qkv, k_cache, v_cache)   # [T, q_size]
+        h = self._all_reduce(self._lora_add_(
+            f"l{i}.o", "o", attn_out, _linear(attn_out, p[f"l{i}.o"]),
+            adapter_idx))
+        h2 = ops.rmsnorm_residual_(h, residual, p[f"l{i}.ln2"], c.rms_eps)
+        gu = self._lora_add_(f"l{i}.gate_up", "gate_up", h2,
+                             _linear(h2, p[f"l{i}.gate_up"]), adapter_idx)
+        act = ops.silu_mul(gu)
+        mlp = self._all_reduce(self._lora_add_(
+            f"l{i}.down", "down", act, _linear(act, p[f"l{i}.down"]),
+            adapter_idx))
+        return mlp, residual
+
     def forward_prefill(self, input_ids: torch.Tensor, positions: torch.Tensor,
                         kv_cache, slot_mapping: torch.Tensor,
-                        cu_seqlens: torch.Tensor) -> torch.Tensor:
+                        cu_seqlens: torch.Tensor,
+                        adapter_idx: Optional[torch.Tensor] = None
+                        ) -> torch.Tensor:
         """Returns logits for the LAST token of each sequence:
         [n_seqs, vocab]."""
         def attn(i, qkv, k_cache, v_cache):
@@ -386,13 +580,16 @@ class LlamaForCausalLM:
                                         self.n_heads, self.n_kv_heads,
                                         self.config.head_dim)
         return self._forward(input_ids, positions, kv_cache, slot_mapping,
-                             attn, last_idx=cu_seqlens[1:].long() - 1)
+                             attn, last_idx=cu_seqlens[1:].long() - 1,
+                             adapter_idx=adapter_idx)
 
     def forward_mixed(self, input_ids: torch.Tensor, positions: torch.Tensor,
                       kv_cache, slot_mapping: torch.Tensor, n_decode: int,
                       block_tables_dec, seq_lens_dec,
                       chunk_row0, chunk_pos0, chunk_nrows, chunk_btrow,
-                      block_tables_pre, sample_idx) -> torch.Tensor:
+                      block_tables_pre, sample_idx,
+                      adapter_idx: Optional[torch.Tensor] = None
+                      ) -> torch.Tensor:
         """Mixed batch: rows [0, n_decode) are decode tokens, the rest
         are prefill-chunk tokens attending over the paged cache
         (chunked prefill).  Returns logits for ``sample_idx`` rows."""
@@ -409,28 +606,31 @@ class LlamaForCausalLM:
                 out[:n_decode] = out_d
             return out
         return self._forward(input_ids, positions, kv_cache, slot_mapping,
-                             attn, last_idx=sample_idx)
+                             attn, last_idx=sample_idx,
+                             adapter_idx=adapter_idx)
 
     def forward_decode(self, input_ids: torch.Tensor, positions: torch.Tensor,
                        kv_cache, slot_mapping: torch.Tensor,
                        block_tables: torch.Tensor,
-                       seq_lens: torch.Tensor) -> torch.Tensor:
+                       seq_lens: torch.Tensor,
+                       adapter_idx: Optional[torch.Tensor] = None
+                       ) -> torch.Tensor:
         """One token per sequence; returns [batch, vocab] logits."""
         def attn(i, qkv, k_cache, v_cache):
             return ops.decode_attn_rope_qkv(
                 qkv, positions, self.cos_sin, k_cache, v_cache, slot_mapping,
                 block_tables, seq_lens, self.scale, self.n_heads)
         return self._forward(input_ids, positions, kv_cache, slot_mapping,
-                             attn, last_idx=None)
+                             attn, last_idx=None, adapter_idx=adapter_idx)
 
     def _forward(self, input_ids, positions, kv_cache, slot_mapping, attn_fn,
-                 last_idx) -> torch.Tensor:
+                 last_idx, adapter_idx=None) -> torch.Tensor:
         p = self.params
         x = F.embedding(input_ids.long(), p["embed"])
         residual = None
         for i in range(self.config.n_layers):
             x, residual = self._layer(i, x, residual, positions, kv_cache,
-                                      slot_mapping, attn_fn)
+                                      slot_mapping, attn_fn, adapter_idx)
         if self.quant == "fp8":
             h8, hs = ops.rmsnorm_residual_fp8(x, residual, p["final_ln"],
                                               self.config.rms_eps)

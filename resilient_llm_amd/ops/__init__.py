@@ -252,6 +252,37 @@ def kv_copy_blocks_(k_cache: torch.Tensor, v_cache: torch.Tensor,
         ref.kv_copy_blocks_(k_cache, v_cache, src, dst)
 
 
+def lora_shrink(x: torch.Tensor, A: torch.Tensor,
+                adapter_idx: torch.Tensor) -> torch.Tensor:
+    """Batched multi-adapter LoRA, first half: y[t, r] = sum_k x[t, k] *
+    A[a(t), r, k] -> [T, R] f32, with a(t) = ``adapter_idx[t]`` (int32;
+    -1 = no adapter: the row does no memory traffic and its y row is
+    unspecified on the device).  A is the stack [n_adapters, R, K] with
+    R = n_slices * r_max <= 192."""
+    if x.is_cuda:
+        _gpu()
+        return torch.ops.rlli.lora_shrink(x, A, adapter_idx)
+    return ref.lora_shrink(x, A, adapter_idx)
+
+
+def lora_expand_add_(out: torch.Tensor, y: torch.Tensor, B: torch.Tensor,
+                     scale: torch.Tensor, slices,
+                     adapter_idx: torch.Tensor) -> torch.Tensor:
+    """Second half, in place on the base GEMM's output: out[t, o] +=
+    scale[a] * sum_j y[t, s*r_max + j] * B[a, o, j], rounded once at the
+    add; s is the slice of output row o under ``slices`` (<= 3 ascending
+    end-exclusive row boundaries, the last == O; q|k|v, gate|up or one
+    slice).  B [n_adapters, O, r_max <= 64], scale [n_adapters] f32.
+    One writer per element: repeated calls are bit-identical.  Rows with
+    adapter_idx -1 are neither read nor written."""
+    if out.is_cuda:
+        _gpu()
+        torch.ops.rlli.lora_expand_add_(out, y, B, scale, list(slices),
+                                        adapter_idx)
+        return out
+    return ref.lora_expand_add_(out, y, B, scale, slices, adapter_idx)
+
+
 def prefill_paged_attn(qkv, k_cache, v_cache, chunk_row0, chunk_pos0,
                        chunk_nrows, chunk_btrow, block_tables,
                        scale: float, n_q: int) -> torch.Tensor:

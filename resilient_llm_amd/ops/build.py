@@ -43,6 +43,7 @@ SOURCES = [
     "sampling.hip",
     "logprobs.hip",
     "kv_copy.hip",
+    "lora.hip",
     "skinny_gemm.hip",
     "skinny2.hip",
     "streamprobe.hip",

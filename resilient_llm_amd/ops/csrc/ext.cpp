@@ -750,6 +750,82 @@ void kv_copy_blocks_(Tensor k_cache, Tensor v_cache, const Tensor& src,
   check_launch("kv_copy_blocks_");
 }
 
+// ------------------------------------------------------------------ lora
+// Batched multi-adapter LoRA (lora.hip).  adapter_idx VALUES are checked
+// on the device: a row whose index is negative or past the stack is a
+// no-adapter row.
+void check_adapter_idx(const Tensor& idx, const Tensor& like, int64_t T) {
+  TORCH_CHECK(idx.scalar_type() == at::kInt && idx.is_contiguous() &&
+              idx.dim() == 1 && idx.numel() == T &&
+              idx.device() == like.device(),
+              "adapter_idx must be contiguous int32 [T] on the data's device");
+}
+
+// y[T, R] f32; rows with adapter_idx -1 are NOT written (unspecified).
+Tensor lora_shrink(const Tensor& x, const Tensor& A,
+                   const Tensor& adapter_idx) {
+  check_bf16_contig(x, "x");
+  check_bf16_contig(A, "A");
+  TORCH_CHECK(x.dim() == 2 && A.dim() == 3 && A.size(2) == x.size(1),
+              "x must be [T, K] and A [n_adapters, R, K]");
+  TORCH_CHECK(A.device() == x.device(), "x/A device mismatch");
+  const int64_t T = x.size(0), K = x.size(1), R = A.size(1);
+  TORCH_CHECK(R >= 1 && R <= 192, "stacked rank R must be in 1..192, got ", R);
+  TORCH_CHECK(K >= 1 && T <= INT32_MAX && K <= INT32_MAX);
+  check_adapter_idx(adapter_idx, x, T);
+  Tensor y = at::empty({T, R}, x.options().dtype(at::kFloat));
+  if (T == 0) return y;
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  rlli::launch_lora_shrink(bf16_ptr(x), bf16_ptr(A),
+                           adapter_idx.data_ptr<int32_t>(),
+                           y.data_ptr<float>(), int(T), int(A.size(0)),
+                           int(R), int(K), current_stream(x));
+  check_launch("lora_shrink");
+  return y;
+}
+
+void lora_expand_add_(Tensor out, const Tensor& y, const Tensor& B,
+                      const Tensor& scale, at::IntArrayRef slices,
+                      const Tensor& adapter_idx) {
+  check_bf16_contig(out, "out");
+  check_bf16_contig(B, "B");
+  TORCH_CHECK(out.dim() == 2 && B.dim() == 3 && B.size(1) == out.size(1),
+              "out must be [T, O] and B [n_adapters, O, r_max]");
+  const int64_t T = out.size(0), O = out.size(1), r_max = B.size(2);
+  const int64_t n_slices = int64_t(slices.size());
+  TORCH_CHECK(r_max >= 1 && r_max <= 64, "r_max must be in 1..64, got ", r_max);
+  TORCH_CHECK(n_slices >= 1 && n_slices <= 3,
+              "slices holds 1..3 end-exclusive row boundaries");
+  int ends[3] = {0, 0, 0};
+  int64_t prev = 0;
+  for (int64_t i = 0; i < n_slices; ++i) {
+    TORCH_CHECK(slices[i] > prev && slices[i] <= O,
+                "slice boundaries must ascend within (0, O]");
+    prev = slices[i];
+    ends[i] = int(slices[i]);
+  }
+  TORCH_CHECK(prev == O, "the last slice boundary must equal O");
+  TORCH_CHECK(y.scalar_type() == at::kFloat && y.is_contiguous() &&
+              y.dim() == 2 && y.size(0) == T &&
+              y.size(1) == n_slices * r_max && y.device() == out.device(),
+              "y must be contiguous f32 [T, n_slices * r_max]");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.is_contiguous() &&
+              scale.dim() == 1 && scale.numel() == B.size(0) &&
+              scale.device() == out.device(),
+              "scale must be contiguous f32 [n_adapters]");
+  TORCH_CHECK(B.device() == out.device(), "out/B device mismatch");
+  TORCH_CHECK(T <= INT32_MAX && O <= INT32_MAX - 256);
+  check_adapter_idx(adapter_idx, out, T);
+  if (T == 0) return;
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(out.device());
+  rlli::launch_lora_expand_add(bf16_ptr(out), y.data_ptr<float>(),
+                               bf16_ptr(B), scale.data_ptr<float>(),
+                               adapter_idx.data_ptr<int32_t>(), int(T),
+                               int(B.size(0)), int(O), int(r_max),
+                               int(n_slices), ends, current_stream(out));
+  check_launch("lora_expand_add_");
+}
+
 }  // namespace
 
 TORCH_LIBRARY(rlli, m) {
@@ -793,6 +869,9 @@ TORCH_LIBRARY(rlli, m) {
         "-> Tensor");
   m.def("kv_copy_blocks_(Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor src, "
         "Tensor dst) -> ()");
+  m.def("lora_shrink(Tensor x, Tensor A, Tensor adapter_idx) -> Tensor");
+  m.def("lora_expand_add_(Tensor(a!) out, Tensor y, Tensor B, Tensor scale, "
+        "int[] slices, Tensor adapter_idx) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(rlli, CUDA, m) {
@@ -818,4 +897,6 @@ TORCH_LIBRARY_IMPL(rlli, CUDA, m) {
   m.impl("stream_probe", &stream_probe);
   m.impl("prefill_paged_attn", &prefill_paged_attn);
   m.impl("kv_copy_blocks_", &kv_copy_blocks_);
+  m.impl("lora_shrink", &lora_shrink);
+  m.impl("lora_expand_add_", &lora_expand_add_);
 }

@@ -190,4 +190,28 @@ void launch_kv_copy_blocks(void* k_cache, void* v_cache, const int32_t* src,
                            int64_t num_blocks, int64_t chunk_bytes,
                            hipStream_t stream);
 
+// Batched multi-adapter LoRA next to the base GEMM (lora.hip): token row
+// t uses adapter adapter_idx[t]; -1 (or an index outside the stack) means
+// no adapter and the row is neither read nor written.
+//   shrink: y[t, r] = sum_k x[t, k] * A[a, r, k]                (f32)
+//   expand: out[t, o] = bf16(float(out[t, o]) + scale[a]
+//                       * sum_j y[t, s*r_max + j] * B[a, o, j])
+// s = the slice of output row o under the ascending end-exclusive
+// slice_ends (host array of n_slices <= 3 entries, the last one == O);
+// R = n_slices * r_max <= 192, r_max <= 64.
+void launch_lora_shrink(const uint16_t* x,            // [T, K] bf16
+                        const uint16_t* A,            // [n_adapters, R, K]
+                        const int32_t* adapter_idx,   // [T]
+                        float* y,                     // [T, R]
+                        int T, int n_adapters, int R, int K,
+                        hipStream_t stream);
+void launch_lora_expand_add(uint16_t* out,            // [T, O] bf16, in place
+                            const float* y,           // [T, R]
+                            const uint16_t* B,        // [n_adapters, O, r_max]
+                            const float* scale,       // [n_adapters]
+                            const int32_t* adapter_idx,
+                            int T, int n_adapters, int O, int r_max,
+                            int n_slices, const int* slice_ends,
+                            hipStream_t stream);
+
 }  // namespace rlli

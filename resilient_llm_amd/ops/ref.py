@@ -253,6 +253,61 @@ def kv_copy_blocks_(k_cache: torch.Tensor, v_cache: torch.Tensor,
         raw[:, d] = raw[:, s]
 
 
+# ---- batched multi-adapter LoRA ----
+# The rounding contract of the HIP kernels (ops/csrc/lora.hip): the shrink
+# result y and the delta stay in f32; there is ONE rounding, to out's
+# dtype, at the final add.  Token row t uses adapter adapter_idx[t]; -1
+# (or an index outside the stack) means no adapter.
+def _adapter_rows(adapter_idx: torch.Tensor, n_adapters: int):
+    idx = adapter_idx.long()
+    for a in torch.unique(idx).tolist():
+        if 0 <= a < n_adapters:
+            yield a, (idx == a).nonzero().squeeze(1)
+
+
+def lora_shrink(x: torch.Tensor, A: torch.Tensor,
+                adapter_idx: torch.Tensor) -> torch.Tensor:
+    """y[t, r] = sum_k x[t, k] * A[a(t), r, k] in f32: x [T, K],
+    A [n_adapters, R, K], adapter_idx [T] int32 -> y [T, R] f32.  Rows
+    without an adapter are zero here (the device op leaves them
+    unwritten; nothing reads them)."""
+    y = torch.zeros((x.shape[0], A.shape[1]), dtype=torch.float32,
+                    device=x.device)
+    for a, rows in _adapter_rows(adapter_idx, A.shape[0]):
+        y[rows] = x[rows].float() @ A[a].float().t()
+    return y
+
+
+def lora_expand_add_(out: torch.Tensor, y: torch.Tensor, B: torch.Tensor,
+                     scale: torch.Tensor, slices,
+                     adapter_idx: torch.Tensor) -> torch.Tensor:
+    """In place: out[t, o] = dtype(float(out[t, o]) + scale[a] * sum_j
+    y[t, s*r_max + j] * B[a, o, j]) with s the slice of output row o under
+    the ascending end-exclusive boundaries ``slices`` (<= 3, the last one
+    == O): out [T, O], y [T, len(slices) * r_max] f32,
+    B [n_adapters, O, r_max], scale [n_adapters] f32.  Rows without an
+    adapter are not touched."""
+    slices = [int(e) for e in slices]
+    O, r_max = B.shape[1], B.shape[2]
+    if not 1 <= len(slices) <= 3 or slices != sorted(set(slices)) \
+            or slices[0] <= 0 or slices[-1] != O or out.shape[1] != O:
+        raise ValueError(f"bad slice table {slices} for O = {O}")
+    if y.shape[1] != len(slices) * r_max:
+        raise ValueError("y width must be len(slices) * r_max")
+    for a, rows in _adapter_rows(adapter_idx, B.shape[0]):
+        yr = y[rows]
+        delta = torch.empty((rows.numel(), O), dtype=torch.float32,
+                            device=out.device)
+        lo = 0
+        for s, hi in enumerate(slices):
+            delta[:, lo:hi] = (yr[:, s * r_max:(s + 1) * r_max]
+                               @ B[a, lo:hi].float().t())
+            lo = hi
+        out[rows] = (out[rows].float()
+                     + scale[a].float() * delta).to(out.dtype)
+    return out
+
+
 # ---- fp8-activation emitters (quantized-weight GEMM path) ----
 def quantize_fp8_rowwise(t: torch.Tensor):
     """Per-row fp8-e4m3 quantization: (q, scales) with q*scales ~= t."""

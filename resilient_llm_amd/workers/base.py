@@ -60,6 +60,10 @@ class GenerationRequest:
     logit_bias: Optional[list] = None
     top_k: int = 0
     min_p: float = 0.0
+    # LoRA adapter (a name loaded on the worker) this request runs under;
+    # the gateway fills it from the deployment's ``adapter``.  None = the
+    # base weights.  Workers without adapters (the stub) ignore it.
+    adapter: Optional[str] = None
 
 
 @dataclasses.dataclass

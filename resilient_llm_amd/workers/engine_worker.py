@@ -80,6 +80,7 @@ class EngineWorker(Worker):
                  kv_dtype: str = "bf16",
                  quant=None,
                  spec_lookup: int = 0,
+                 adapters: Optional[dict] = None,
                  seed: int = 0) -> None:
         super().__init__(device=device_label or f"gpu:{device}",
                          models={model_name})
@@ -99,6 +100,10 @@ class EngineWorker(Worker):
             from ..utils.logging import log_with_timestamp
             log_with_timestamp(f"{self.device}: loaded {n} tensors from "
                                f"{weights} (tp {tp_rank}/{tp_world})", "grey")
+        # LoRA adapters {name: PEFT directory}: loaded once at start and
+        # stacked on the device; a request picks one by name
+        for a_name, a_path in (adapters or {}).items():
+            self.model.load_adapter(a_name, a_path)
         self.tokenizer = load_tokenizer(weights, config.vocab_size)
         # EOS precedence: explicit deployment override > tokenizer-declared
         # ids (real HF tokenizer) > model-preset ids
@@ -312,6 +317,8 @@ class EngineWorker(Worker):
     def _enqueue(self, req: GenerationRequest,
                  mode: str = "stream") -> tuple[str, asyncio.Queue, int]:
         self._check_fault()
+        if req.adapter is not None and self.tp_control is not None:
+            raise WorkerError("LoRA adapters are not supported on TP pools")
         prompt_ids = self.tokenizer.encode(render_prompt(req.messages))
         params = self._params_of(req)
         self._req_counter += 1
@@ -336,10 +343,19 @@ class EngineWorker(Worker):
                 self.tp_control.submit(
                     ("add", rid, prompt_ids, dataclasses.asdict(params)))
             else:
-                self.engine.add_request(rid, prompt_ids, params)
+                # adapter-free requests make exactly the call they always did
+                lora = {} if req.adapter is None else {"adapter": req.adapter}
+                self.engine.add_request(rid, prompt_ids, params, **lora)
         except CapacityExceeded as e:
             del self._sinks[rid]
             raise WorkerThrottled(str(e)) from e
+        except ValueError as e:
+            if req.adapter is None:
+                raise
+            # an adapter this worker has not loaded: a hard error of this
+            # worker (the gateway fails over), never a run on base weights
+            del self._sinks[rid]
+            raise WorkerError(str(e)) from e
         self._work_event.set()
         return rid, q, len(prompt_ids)
 
@@ -384,13 +400,18 @@ class EngineWorker(Worker):
                     ("add_group", rids, prompt_ids,
                      [dataclasses.asdict(p) for p in params_list]))
             else:
-                self.engine.add_request_group(rids, prompt_ids, params_list)
+                lora = {} if reqs[0].adapter is None \
+                    else {"adapter": reqs[0].adapter}
+                self.engine.add_request_group(rids, prompt_ids, params_list,
+                                              **lora)
         except BaseException as e:
             for rid in rids:
                 self._sinks.pop(rid, None)
             self._group_rids.difference_update(rids)
             if isinstance(e, CapacityExceeded):
                 raise WorkerThrottled(str(e)) from e
+            if isinstance(e, ValueError) and reqs[0].adapter is not None:
+                raise WorkerError(str(e)) from e
             raise
         self._work_event.set()
         return rids, queues, len(prompt_ids)
@@ -777,6 +798,7 @@ class EngineWorker(Worker):
         return {"device": self.device, "status": "ok",
                 "models": sorted(self.models),
                 "model": self.model_name,
+                "adapters": list(self.model.adapter_names),
                 "in_flight": self._in_flight,
                 "queued": len(self.engine.waiting),
                 "running": len(self.engine.running),

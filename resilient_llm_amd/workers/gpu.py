@@ -36,6 +36,7 @@ def spawn_gpu_worker(device_index: str, model_name: str,
                      kv_dtype: str | None = None,
                      quant: str | None = None,
                      spec_lookup: int | None = None,
+                     adapters: dict | None = None,
                      extra_env: dict | None = None) -> subprocess.Popen:
     """``device_index`` may be a sub-device replica like ``0.1``: several
     worker processes co-located on physical GPU 0 — 288 GB of HBM3E holds
@@ -66,6 +67,8 @@ def spawn_gpu_worker(device_index: str, model_name: str,
         cmd += ["--quant", str(quant)]
     if spec_lookup:
         cmd += ["--spec-lookup", str(spec_lookup)]
+    for name, path in (adapters or {}).items():
+        cmd += ["--adapter", f"{name}={path}"]
     return subprocess.Popen(cmd, env=env)
 
 
@@ -117,6 +120,8 @@ def register_gpu_workers(config: Config, registry: WorkerRegistry,
         kv_dtype = extra.get("kv_dtype")
         quant = extra.get("quantization")
         spec = extra.get("spec_lookup")
+        # every alias on this worker may declare adapters: the union loads
+        adapters = config.worker_adapters("gpu", target)
         eos = extra.get("eos_id")
         eos_list = None if eos is None else (
             [int(eos)] if isinstance(eos, int) else [int(e) for e in eos])
@@ -124,16 +129,19 @@ def register_gpu_workers(config: Config, registry: WorkerRegistry,
                                 max_batch=max_batch, use_graphs=use_graphs,
                                 weights=weights, eos_ids=eos_list,
                                 kv_dtype=kv_dtype, quant=quant,
-                                spec_lookup=spec, target_step_ms=slo)
+                                spec_lookup=spec, adapters=adapters,
+                                target_step_ms=slo)
         client = RpcWorkerClient(f"gpu:{target}", {model_name}, sock)
         client.proc = proc
-        client.respawn = (lambda t=target, m=model_name, s=sock:
+        client.respawn = (lambda t=target, m=model_name, s=sock,
+                          adapters=adapters:
                           spawn_gpu_worker(t, m, s, kv_gb=kv_gb,
                                            max_batch=max_batch,
                                            use_graphs=use_graphs,
                                            weights=weights, eos_ids=eos_list,
                                            kv_dtype=kv_dtype, quant=quant,
                                            spec_lookup=spec,
+                                           adapters=adapters,
                                            target_step_ms=slo))
         registry.register("gpu", target, client)
 

@@ -35,6 +35,10 @@ def main() -> None:
     ap.add_argument("--kv-dtype", default="bf16", choices=("bf16", "fp8"),
                     help="paged-KV-cache element type: fp8-e4m3 halves "
                          "bytes/token (2x KV capacity per GiB)")
+    ap.add_argument("--adapter", action="append", default=None,
+                    metavar="NAME=PATH",
+                    help="LoRA adapter (PEFT directory) to load at start; "
+                         "repeatable")
     ap.add_argument("--device", default=None,
                     help="torch device override (tests: cpu)")
     args = ap.parse_args()
@@ -68,6 +72,8 @@ def main() -> None:
                               kv_dtype=args.kv_dtype,
                               quant=args.quant,
                               spec_lookup=args.spec_lookup,
+                              adapters=dict(a.split("=", 1)
+                                            for a in args.adapter or ()),
                               target_step_ms=args.target_step_ms)
         log_with_timestamp(
             f"worker {args.device_label} ready: {args.model} on {device}, "
