@@ -177,9 +177,9 @@ def _parse_deployment(entry: Any, idx: int) -> Deployment:
                  f"model_list[{idx}].litellm_params.kv_dtype must be "
                  f"bf16|fp8, got {extra['kv_dtype']!r}")
     if "quantization" in extra:
-        _require(extra["quantization"] in ("fp8",),
+        _require(extra["quantization"] in ("fp8", "int4"),
                  f"model_list[{idx}].litellm_params.quantization must be "
-                 f"fp8, got {extra['quantization']!r}")
+                 f"fp8|int4, got {extra['quantization']!r}")
     if "spec_lookup" in extra:
         _require(isinstance(extra["spec_lookup"], int)
                  and 0 <= extra["spec_lookup"] <= 16,
@@ -306,12 +306,14 @@ def load_config(path: str | os.PathLike[str] | None = None,
                      f"{d.backend_kind}/{d.backend_target} "
                      f"({sorted(loaded) or 'none'})")
         if loaded:
-            _require(not any(e.params.get("quantization") == "fp8"
-                             for e in on_worker),
+            quants = sorted({e.params["quantization"] for e in on_worker
+                             if e.params.get("quantization")})
+            _require(not quants,
                      f"deployment {d.model_name}: adapters cannot be "
-                     f"combined with quantization: fp8 on "
+                     f"combined with quantization: {'|'.join(quants)} on "
                      f"{d.backend_kind}/{d.backend_target} (the fp8 path "
-                     f"hands the MLP fp8 activations)")
+                     f"hands the MLP fp8 activations, the int4 path has no "
+                     f"bf16 base GEMM to add to)")
             if d.backend_kind == "pool":
                 _require(cluster.pools[d.backend_target].tensor_parallel == 1,
                          f"deployment {d.model_name}: adapters are not "

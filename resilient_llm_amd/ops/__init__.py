@@ -335,4 +335,53 @@ def skinny2_silu_linear(gu: torch.Tensor, w: torch.Tensor,
     return torch.nn.functional.linear(ref.silu_mul(gu), w)
 
 
+def w4a16_linear(x: torch.Tensor, packed: torch.Tensor, s: torch.Tensor,
+                 splitk: int = 0, out: torch.Tensor | None = None,
+                 ws: torch.Tensor | None = None) -> torch.Tensor:
+    """Fused int4-weight GEMM for decode rows: out[m, n] = bf16(sum_g
+    s[n, g] * sum_{k in g} x[m, k] * q[n, k]), x [M, K] bf16 with
+    1 <= M <= 64, ``packed`` / ``s`` from ``ref.w4_pack`` /
+    ``ref.quantize_w4`` (group 128 along K; K % 128 == 0, N % 64 == 0).
+    Row m depends on row m of x only and is bit-identical for every M;
+    no atomics.  ``splitk`` <= 0 picks the K-slicing from (N, K)
+    (``w4a16_plan``).  ``out`` [M, N] bf16 is written in full and nothing
+    else is, apart from the split-K slab: the first slices*M*N floats of
+    ``ws`` when given, else a tensor the op allocates."""
+    if x.is_cuda:
+        _gpu()
+        if out is None:
+            out = torch.empty((x.shape[0], s.shape[0]), dtype=x.dtype,
+                              device=x.device)
+        torch.ops.rlli.w4a16_linear_(x, packed, s, splitk, out, ws)
+        return out
+    y = ref.w4a16_linear(x, packed, s)
+    if out is None:
+        return y
+    out.copy_(y)
+    return out
+
+
+def w4a16_plan(N: int, K: int, splitk: int = 0) -> tuple[int, int]:
+    """(slices, k per slice) ``w4a16_linear`` runs with on the GPU: K is
+    cut in whole 128-k groups, ceil(groups / slices) per slice."""
+    _gpu()
+    sk, kps = torch.ops.rlli.w4a16_plan(N, K, splitk)
+    return int(sk), int(kps)
+
+
+def w4_dequant(packed: torch.Tensor, s: torch.Tensor,
+               out: torch.Tensor | None = None) -> torch.Tensor:
+    """bf16 [N, K] = bf16(f32(s) * q) of an int4 weight, into ``out``
+    when given (a caller-owned scratch buffer) — the path for more rows
+    than the fused kernel takes."""
+    if packed.is_cuda:
+        _gpu()
+        if out is None:
+            out = torch.empty((s.shape[0], s.shape[1] * ref.W4_GROUP),
+                              dtype=torch.bfloat16, device=packed.device)
+        torch.ops.rlli.w4_dequant_(packed, s, out)
+        return out
+    return ref.w4_dequant(packed, s, out)
+
+
 build_cos_sin = ref.build_cos_sin

@@ -46,6 +46,7 @@ SOURCES = [
     "lora.hip",
     "skinny_gemm.hip",
     "skinny2.hip",
+    "w4a16.hip",
     "streamprobe.hip",
 ]
 HEADERS = ["common.h", "kernels.h"]

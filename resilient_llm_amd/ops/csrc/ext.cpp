@@ -569,6 +569,98 @@ Tensor skinny2_silu_linear(const Tensor& gu, const Tensor& w, int64_t splitk) {
   return out;
 }
 
+// --------------------------------------------------------------- w4a16
+// int4 group-quantized weights: packed int32 [N*K/8] in the fragment
+// order of ops/ref.py w4_pack, s bf16 [N, K/128].
+void check_w4(const Tensor& packed, const Tensor& s, const Tensor& like) {
+  TORCH_CHECK(s.dim() == 2 && s.size(0) >= 1 && s.size(1) >= 1,
+              "s must be [N, K/128]");
+  check_bf16_contig(s, "s");
+  const int64_t N = s.size(0), K = s.size(1) * 128;
+  TORCH_CHECK(N % 64 == 0, "int4 weights need N % 64 == 0, got N=", N);
+  TORCH_CHECK(N * K / 2 < (int64_t(1) << 31), "int4 weight too large");
+  TORCH_CHECK(packed.scalar_type() == at::kInt && packed.is_contiguous() &&
+              packed.is_cuda(), "packed must be contiguous int32 on the GPU");
+  TORCH_CHECK(packed.numel() == N * K / 8, "packed must hold N*K/8 = ",
+              N * K / 8, " elements, got ", packed.numel());
+  TORCH_CHECK(packed.device() == like.device() &&
+              s.device() == like.device(), "device mismatch");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(packed.data_ptr()) % 16 == 0,
+              "packed must be 16-byte aligned");
+}
+
+// the K-slicing w4a16_linear runs with: [slices, k per slice]
+std::vector<int64_t> w4a16_plan(int64_t N, int64_t K, int64_t splitk) {
+  TORCH_CHECK(N >= 64 && N % 64 == 0 && K >= 128 && K % 128 == 0 &&
+              N < (int64_t(1) << 24) && K < (int64_t(1) << 24),
+              "w4a16 needs N % 64 == 0 and K % 128 == 0");
+  int sk = 1, gps = 1;
+  rlli::w4a16_plan(int(N), int(K), int(splitk), &sk, &gps);
+  return {sk, int64_t(gps) * 128};
+}
+
+// out [M, N] bf16 is written in full and nothing else is, apart from the
+// first slices*M*N floats of the split-K slab: ``ws`` when the caller
+// owns one (>= that many f32), else a caching-allocator tensor, which
+// inside hipGraph capture comes from the graph's pool.
+void w4a16_linear_(const Tensor& x, const Tensor& packed, const Tensor& s,
+                   int64_t splitk, Tensor out,
+                   const c10::optional<Tensor>& ws_opt) {
+  check_bf16_contig(x, "x");
+  check_bf16_contig(out, "out");
+  TORCH_CHECK(x.dim() == 2, "x must be [M, K]");
+  check_w4(packed, s, x);
+  const int M = int(x.size(0));
+  const int K = int(x.size(1));
+  const int N = int(s.size(0));
+  TORCH_CHECK(M >= 1 && M <= 64, "w4a16_linear needs 1 <= M <= 64, got ", M);
+  TORCH_CHECK(K % 128 == 0 && K >= 128,
+              "w4a16_linear needs K % 128 == 0, got K=", K);
+  TORCH_CHECK(s.size(1) * 128 == K, "x/s K mismatch: x has K=", K,
+              ", s has ", s.size(1), " groups");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "x must be 16-byte aligned");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == M && out.size(1) == N &&
+              out.device() == x.device(), "out must be [M, N] = [", M, ", ",
+              N, "] on x's device");
+  int sk = 1, gps = 1;
+  rlli::w4a16_plan(N, K, int(splitk), &sk, &gps);
+  Tensor ws;
+  float* ws_ptr = nullptr;
+  if (sk > 1) {
+    if (ws_opt.has_value()) {
+      ws = *ws_opt;
+      TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.is_contiguous() &&
+                  ws.device() == x.device() &&
+                  ws.numel() >= int64_t(sk) * M * N,
+                  "ws must be contiguous f32 with >= slices*M*N = ",
+                  int64_t(sk) * M * N, " elements on x's device");
+    } else {
+      ws = at::empty({sk, M, N}, x.options().dtype(at::kFloat));
+    }
+    ws_ptr = ws.data_ptr<float>();
+  }
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  rlli::launch_w4a16(bf16_ptr(x),
+                     reinterpret_cast<const uint32_t*>(packed.data_ptr()),
+                     bf16_ptr(s), ws_ptr, bf16_ptr(out), M, N, K, sk, gps,
+                     current_stream(x));
+  check_launch("w4a16_linear");
+}
+
+void w4_dequant_(const Tensor& packed, const Tensor& s, Tensor out) {
+  check_bf16_contig(out, "out");
+  check_w4(packed, s, out);
+  const int64_t N = s.size(0), K = s.size(1) * 128;
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == N && out.size(1) == K,
+              "out must be [N, K] = [", N, ", ", K, "]");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(out.device());
+  rlli::launch_w4_dequant(
+      reinterpret_cast<const uint32_t*>(packed.data_ptr()), bf16_ptr(s),
+      bf16_ptr(out), int(N), int(K), current_stream(out));
+  check_launch("w4_dequant_");
+}
+
 Tensor stream_probe(const Tensor& w, int64_t splitk) {
   check_bf16_contig(w, "w");
   Tensor sink = at::zeros({256}, w.options().dtype(at::kFloat));
@@ -862,6 +954,10 @@ TORCH_LIBRARY(rlli, m) {
   m.def("skinny_linear(Tensor x, Tensor w) -> Tensor");
   m.def("skinny2_linear(Tensor x, Tensor w, int splitk) -> Tensor");
   m.def("skinny2_silu_linear(Tensor gu, Tensor w, int splitk) -> Tensor");
+  m.def("w4a16_linear_(Tensor x, Tensor packed, Tensor s, int splitk, "
+        "Tensor(a!) out, Tensor(b!)? ws) -> ()");
+  m.def("w4a16_plan(int N, int K, int splitk) -> int[]", &w4a16_plan);
+  m.def("w4_dequant_(Tensor packed, Tensor s, Tensor(a!) out) -> ()");
   m.def("stream_probe(Tensor w, int splitk) -> Tensor");
   m.def("prefill_paged_attn(Tensor qkv, Tensor k_cache, Tensor v_cache, "
         "Tensor chunk_row0, Tensor chunk_pos0, Tensor chunk_nrows, "
@@ -894,6 +990,8 @@ TORCH_LIBRARY_IMPL(rlli, CUDA, m) {
   m.impl("skinny_linear", &skinny_linear);
   m.impl("skinny2_linear", &skinny2_linear);
   m.impl("skinny2_silu_linear", &skinny2_silu_linear);
+  m.impl("w4a16_linear_", &w4a16_linear_);
+  m.impl("w4_dequant_", &w4_dequant_);
   m.impl("stream_probe", &stream_probe);
   m.impl("prefill_paged_attn", &prefill_paged_attn);
   m.impl("kv_copy_blocks_", &kv_copy_blocks_);

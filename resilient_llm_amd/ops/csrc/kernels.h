@@ -119,6 +119,22 @@ void launch_skinny2_silu(const uint16_t* gu, const uint16_t* w, float* ws,
                          uint16_t* out, int M, int N, int K, int splitk,
                          hipStream_t stream);
 
+// W4A16 (w4a16.hip): int4 group-quantized weights (group 128 along K,
+// symmetric, bf16 scales s[N, K/128]) in the fragment-order packing of
+// ops/ref.py w4_pack; K % 128 == 0, N % 64 == 0.
+//   launch_w4a16: out[M,N] = bf16(sum_g s * sum_{k in g} x * q), M <= 64;
+//     ws is the [splitk, M, N] f32 slab when splitk > 1.  w4a16_plan
+//     gives the slicing (whole groups per slice, a function of N and K
+//     only); splitk_req <= 0 picks the grid-fill heuristic.
+//   launch_w4_dequant: out[N,K] = bf16(f32(s) * q).
+void w4a16_plan(int N, int K, int splitk_req, int* splitk,
+                int* grp_per_slice);
+void launch_w4a16(const uint16_t* x, const uint32_t* packed,
+                  const uint16_t* s, float* ws, uint16_t* out, int M, int N,
+                  int K, int splitk, int grp_per_slice, hipStream_t stream);
+void launch_w4_dequant(const uint32_t* packed, const uint16_t* s,
+                       uint16_t* out, int N, int K, hipStream_t stream);
+
 void launch_skinny_gemm(const uint16_t* x, const uint16_t* w, float* ws,
                         uint16_t* out, int M, int N, int K, int splitk,
                         hipStream_t stream);

@@ -338,3 +338,99 @@ def scaled_mm_ref(x8, xs, w8, ws):
     xf = x8.float() * xs.reshape(-1, 1)
     wf = w8.float() * ws.reshape(-1, 1)
     return (xf @ wf.t()).to(torch.bfloat16)
+
+
+# ---- int4 group-quantized weights (W4A16) ----
+# Symmetric, group-wise along K (group = 128): s[n, g] = bf16(max|W| / 7),
+# q = clamp(rne(W / s), -8, 7).  ``packed`` is an opaque int32 tensor of
+# N*K/8 elements in MFMA fragment order (mfma_f32_16x16x32_bf16): the
+# four dwords at ((tile * G + g) * 64 + lane) * 4, tile = n // 16,
+# lane = o * 16 + n % 16, hold lane's k-octet o of the four 32-k granules
+# of group g — one 16-byte load per lane feeds 4 MFMAs and ends on a scale
+# boundary, and a wave's load of one (tile, group) is 1 KiB contiguous.
+# Dword j holds k = g*128 + j*32 + o*8 + i, i = 0..7, as the nibble
+# u = q + 8 at bit 4*(i//2) + 16*(i%2): ``(d >> 4p) & 0x000F000F |
+# 0x43004300`` is then the bf16 pair (128 + u) of elements 2p, 2p+1.
+W4_GROUP = 128
+_W4_SHIFTS = (0, 16, 4, 20, 8, 24, 12, 28)
+
+
+def _w4_check_shape(N: int, K: int) -> None:
+    if N <= 0 or K <= 0 or N % 64 or K % W4_GROUP:
+        raise ValueError(f"int4 weights need N % 64 == 0 and K % 128 == 0, "
+                         f"got N={N} K={K}")
+
+
+def quantize_w4(w: torch.Tensor):
+    """W [N, K] -> (q int8 [N, K] in -8..7, s bf16 [N, K/128]).  An
+    all-zero group gets the smallest positive normal bf16 as its scale."""
+    N, K = w.shape
+    _w4_check_shape(N, K)
+    f = w.float().reshape(N, K // W4_GROUP, W4_GROUP)
+    tiny = torch.finfo(torch.bfloat16).tiny
+    s = (f.abs().amax(dim=-1) / 7.0).to(torch.bfloat16)
+    s = torch.where(s.float() < tiny, torch.full_like(s, tiny), s)
+    q = torch.round(f / s.float().unsqueeze(-1)).clamp_(-8, 7)
+    return q.reshape(N, K).to(torch.int8), s.contiguous()
+
+
+def w4_pack(q: torch.Tensor) -> torch.Tensor:
+    """q int8 [N, K] in -8..7 -> opaque int32 [N*K/8] (layout above)."""
+    N, K = q.shape
+    _w4_check_shape(N, K)
+    G = K // W4_GROUP
+    u = (q.to(torch.int64) + 8)
+    if int(u.min()) < 0 or int(u.max()) > 15:
+        raise ValueError("w4_pack: q must be in -8..7")
+    # [tile, c, g, j, o, i] -> [tile, g, o, c, j, i]
+    u = u.reshape(N // 16, 16, G, 4, 4, 8).permute(0, 2, 4, 1, 3, 5)
+    shifts = torch.tensor(_W4_SHIFTS, dtype=torch.int64, device=q.device)
+    d = (u << shifts).sum(dim=-1)                  # 0 .. 2^32 - 1
+    d = torch.where(d >= 2 ** 31, d - 2 ** 32, d)  # two's-complement int32
+    return d.to(torch.int32).reshape(-1).contiguous()
+
+
+def w4_unpack(packed: torch.Tensor, N: int, K: int) -> torch.Tensor:
+    """Inverse of ``w4_pack``: int8 [N, K] in -8..7."""
+    _w4_check_shape(N, K)
+    if packed.dtype != torch.int32 or packed.numel() != N * K // 8:
+        raise ValueError(f"packed must be int32 with N*K/8 = {N * K // 8} "
+                         f"elements, got {packed.dtype} x {packed.numel()}")
+    G = K // W4_GROUP
+    d = packed.to(torch.int64).reshape(N // 16, G, 4, 16, 4, 1)
+    shifts = torch.tensor(_W4_SHIFTS, dtype=torch.int64, device=packed.device)
+    u = (d >> shifts) & 15                         # [tile, g, o, c, j, i]
+    q = (u - 8).permute(0, 3, 1, 4, 2, 5)          # [tile, c, g, j, o, i]
+    return q.reshape(N, K).to(torch.int8).contiguous()
+
+
+def _w4_shape(packed: torch.Tensor, s: torch.Tensor):
+    N, G = s.shape
+    return N, G * W4_GROUP
+
+
+def w4a16_linear(x: torch.Tensor, packed: torch.Tensor,
+                 s: torch.Tensor) -> torch.Tensor:
+    """The semantic contract of the fused op: out[m, n] = round(sum_g
+    f32(s[n, g]) * sum_{k in g} f32(x[m, k]) * q[n, k]) — integer weights
+    enter the products unrounded, the scale multiplies each group's
+    partial sum, one rounding at the end (to x's dtype: bf16 in, bf16
+    out)."""
+    N, K = _w4_shape(packed, s)
+    G = K // W4_GROUP
+    q = w4_unpack(packed, N, K).float().reshape(N, G, W4_GROUP)
+    xf = x.float().reshape(x.shape[0], G, W4_GROUP)
+    part = torch.einsum("mgk,ngk->mng", xf, q)
+    return (part * s.float().unsqueeze(0)).sum(dim=-1).to(x.dtype)
+
+
+def w4_dequant(packed: torch.Tensor, s: torch.Tensor,
+               out: torch.Tensor | None = None) -> torch.Tensor:
+    """bf16 [N, K] = bf16(f32(s) * q): one rounding per weight."""
+    N, K = _w4_shape(packed, s)
+    q = w4_unpack(packed, N, K).float().reshape(N, K // W4_GROUP, W4_GROUP)
+    w = (q * s.float().unsqueeze(-1)).reshape(N, K).to(torch.bfloat16)
+    if out is None:
+        return w
+    out.copy_(w)
+    return out

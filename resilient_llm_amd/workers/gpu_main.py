@@ -29,9 +29,10 @@ def main() -> None:
     ap.add_argument("--spec-lookup", type=int, default=0,
                     help="prompt-lookup speculative decoding depth "
                          "(greedy requests; 0 = off)")
-    ap.add_argument("--quant", default=None, choices=(None, "fp8"),
-                    help="W8A8-fp8 weight quantization for gate_up/down/"
-                         "lm_head (rowwise scaled_mm)")
+    ap.add_argument("--quant", default=None, choices=(None, "fp8", "int4"),
+                    help="fp8: W8A8-fp8 weights for gate_up/down/lm_head "
+                         "(rowwise scaled_mm); int4: W4A16 group-128 "
+                         "weights for qkv/o/gate_up/down (fused HIP GEMM)")
     ap.add_argument("--kv-dtype", default="bf16", choices=("bf16", "fp8"),
                     help="paged-KV-cache element type: fp8-e4m3 halves "
                          "bytes/token (2x KV capacity per GiB)")
