@@ -39,7 +39,6 @@ SOURCES = [
     "decode_attn.hip",
     "prefill_attn.hip",
     "prefill_mfma.hip",
-    "prefill_paged.hip",
     "sampling.hip",
     "logprobs.hip",
     "kv_copy.hip",

@@ -87,7 +87,9 @@ void launch_prefill_attn(
     int head_dim, float scale, int q_stride, int kv_stride,
     hipStream_t stream);
 
-// MFMA varlen causal prefill attention over a fused qkv tensor.
+// MFMA varlen causal prefill attention, K/V read from the fused in-batch
+// qkv tensor.  Shares its tile body with launch_prefill_paged
+// (prefill_mfma.hip); only the K/V source differs.
 void launch_prefill_mfma(const uint16_t* qkv, const int32_t* chunk_t0,
                          const int32_t* chunk_seq_start,
                          const int32_t* chunk_seq_end, uint16_t* out,
@@ -95,7 +97,9 @@ void launch_prefill_mfma(const uint16_t* qkv, const int32_t* chunk_t0,
                          int head_dim, int qkv_stride, float scale,
                          hipStream_t stream);
 
-// MFMA chunked-prefill attention over the paged cache (mixed batches).
+// MFMA chunked-prefill attention, K/V read from the paged cache (bf16 or
+// fp8) through block tables: chunked prefill and mixed batches.  The same
+// tile body as launch_prefill_mfma.
 void launch_prefill_paged(const uint16_t* qkv, const void* k_cache,
                           const void* v_cache, const int32_t* chunk_row0,
                           const int32_t* chunk_pos0,

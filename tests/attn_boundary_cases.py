@@ -333,6 +333,34 @@ def prefill_qkv(kind: str, n_q: int, n_kv: int, D: int, lens=PREFILL_LENS):
                      dim=1).to(torch.bfloat16).contiguous()
 
 
+def prefill_as_paged(qkv, n_q: int, n_kv: int, D: int, lens=PREFILL_LENS,
+                     seed: int = 0):
+    """The packed bf16 batch ``qkv`` restated for the paged entry: a bf16
+    cache that holds each sequence's own K/V behind a shuffled block
+    table (one table row per sequence; every other slot holds the spare
+    code), and each sequence cut into chunks of <= 32 rows (row0 = t,
+    pos0 = t - cu[s], btrow = s).  Returns (k_cache, v_cache,
+    block_table, chunks) with ``chunks`` a dict of int32 tensors."""
+    pos, _, cu = prefill_positions(lens)
+    T, n = len(pos), len(lens)
+    g = torch.Generator().manual_seed(seed)
+    n_phys = n * N_TBL + 1
+    bt = torch.randperm(n_phys, generator=g)[:-1] \
+        .reshape(n, N_TBL).to(torch.int32).contiguous()
+    seq = torch.repeat_interleave(torch.arange(n), torch.tensor(lens))
+    phys = bt.long()[seq, pos // BS]
+    kc = torch.full((n_phys, n_kv, BS, D), SPARE_V, dtype=torch.bfloat16)
+    vc = kc.clone()
+    kc[phys, :, pos % BS] = qkv[:, n_q * D:(n_q + n_kv) * D].reshape(T, n_kv, D)
+    vc[phys, :, pos % BS] = qkv[:, (n_q + n_kv) * D:].reshape(T, n_kv, D)
+    cu = cu.tolist()
+    rows = [(t, t - cu[s], min(32, cu[s + 1] - t), s)
+            for s in range(n) for t in range(cu[s], cu[s + 1], 32)]
+    chunks = {name: torch.tensor([r[i] for r in rows], dtype=torch.int32)
+              for i, name in enumerate(("row0", "pos0", "nrows", "btrow"))}
+    return kc, vc, bt, chunks
+
+
 # ----------------------------------------------------- paged-prefill cases
 # (block-table row, pos0, nrows); engine-style <= 32-row kernel chunks
 PAGED_CHUNKS = [

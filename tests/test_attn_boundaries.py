@@ -1,5 +1,6 @@
 """Boundary-exact tests of the attention kernels (decode_attn.hip,
-prefill_mfma.hip, prefill_attn.hip, prefill_paged.hip, rope_kv.hip).
+prefill_mfma.hip with its in-batch and paged entries, prefill_attn.hip,
+rope_kv.hip).
 
 Random inputs go blind with length: at the project's bf16 tolerance a
 reference that attends to one key too many passes at L = 300.  These
@@ -446,6 +447,33 @@ def test_prefill_paged_random_vs_ref(shape, dtype):
                                  *_paged_args(ch), bt.to(DEV), scale, n_q)
     check(out.cpu()[ch["rows"]], want[ch["rows"]], "needle", ch["pos"] + 1,
           "prefill_paged_attn random")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", C.PREFILL_SHAPES, ids=_id)
+def test_prefill_entries_agree_bitwise(shape):
+    """prefill_attn_qkv and prefill_paged_attn share one tile body, so on
+    a bf16 cache that holds the batch's own K/V (the bf16 codec is the
+    identity) they give the same bits for every row."""
+    n_q, n_kv, D = shape
+    _, _, cu = C.prefill_positions()
+    T = int(cu[-1])
+    g = torch.Generator().manual_seed(3)
+    qkv = torch.randn(T, (n_q + 2 * n_kv) * D, generator=g).to(BF16)
+    kc, vc, bt, ch = C.prefill_as_paged(qkv, n_q, n_kv, D)
+    covered = torch.zeros(T, dtype=torch.int64)
+    for r0, n in zip(ch["row0"].tolist(), ch["nrows"].tolist()):
+        assert 1 <= n <= 32
+        covered[r0:r0 + n] += 1
+    assert (covered == 1).all(), "chunks must cover every row exactly once"
+    scale = 1 / math.sqrt(D)
+    batch = ops.prefill_attn_qkv(qkv.to(DEV), cu.to(DEV), scale, n_q, n_kv, D)
+    paged = ops.prefill_paged_attn(qkv.to(DEV), kc.to(DEV), vc.to(DEV),
+                                   *_paged_args(ch), bt.to(DEV), scale, n_q)
+    differ = (raw(batch.cpu()) != raw(paged.cpu())).any(dim=1)
+    assert not differ.any(), (
+        f"{int(differ.sum())} rows differ in their bits, first "
+        f"{differ.nonzero().flatten().tolist()[:12]}")
 
 
 @pytest.mark.gpu
