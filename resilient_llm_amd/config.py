@@ -185,6 +185,14 @@ def _parse_deployment(entry: Any, idx: int) -> Deployment:
                  and 0 <= extra["spec_lookup"] <= 16,
                  f"model_list[{idx}].litellm_params.spec_lookup must be "
                  f"an int in [0, 16], got {extra['spec_lookup']!r}")
+    if "device_sampling" in extra:
+        _require(isinstance(extra["device_sampling"], bool),
+                 f"model_list[{idx}].litellm_params.device_sampling must "
+                 f"be a bool, got {extra['device_sampling']!r}")
+        # the TP lockstep op stream does not carry the history tensors
+        _require(kind != "pool",
+                 f"model_list[{idx}].litellm_params.device_sampling is "
+                 f"served by gpu/<device> workers only, not by {model!r}")
     # LoRA: ``adapters`` {name: PEFT directory} loads on the worker at
     # start, ``adapter`` names the one this deployment serves
     if "adapters" in extra:

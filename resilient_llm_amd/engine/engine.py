@@ -133,6 +133,7 @@ class LLMEngine:
                  target_step_ms: Optional[float] = None,
                  eos_ids=None,
                  spec_lookup: int = 0,
+                 device_sampling: bool = False,
                  seed: int = 0) -> None:
         self.model = model
         self.kv = kv_cache
@@ -178,6 +179,12 @@ class LLMEngine:
         # nothing to roll back: their KV slots are simply rewritten when
         # the real tokens are fed.
         self.spec_lookup = spec_lookup
+        # opt-in: top_p and presence/frequency-penalty rows are served by
+        # ops.sample_nucleus on the device instead of _sample_torch, so a
+        # batch holding one keeps its sync-free decode step.  Such a row
+        # draws by Gumbel-max like every other device row: same
+        # distribution as the default mode, a different stream per seed
+        self.device_sampling = device_sampling
         self._prefill_budget = max_prefill_tokens
         self._budget_floor = min(max_prefill_tokens, 256)
         self.step_count = 0
@@ -866,8 +873,13 @@ class LLMEngine:
         if cs_plan is not None:
             toks = self._apply_constrained(logits, cs_plan, temps, seeds, 0,
                                            toks)
-        special = [i for i, s in enumerate(seqs)
-                   if s.params.needs_torch_sampling]
+        if self.device_sampling:
+            # throw-away history from output_ids: nothing is appended
+            nuc_plan = self._nuc_plan(seqs)
+            if nuc_plan is not None:
+                toks = self._apply_nucleus(logits, nuc_plan, temps, seeds, 0,
+                                           toks, append=False)
+        special = [i for i, s in enumerate(seqs) if self._torch_row(s)]
         if special:
             toks = toks.clone()
             for i in special:
@@ -905,6 +917,76 @@ class LLMEngine:
                 i32([seqs[i].params.top_k for i in idx]),
                 f32([seqs[i].params.min_p for i in idx]),
                 i32(offs), i32(ids), f32(vals))
+
+    def _nucleus_row(self, s: SeqState) -> bool:
+        """The routing decision of device_sampling: a row that needs
+        top_p or a penalty goes to ops.sample_nucleus — with its bias,
+        top_k and min_p, so no row pays both device ops — unless it has
+        a penalty and may emit more tokens than a history slot holds."""
+        p = s.params
+        return (self.device_sampling and p.needs_torch_sampling
+                and (p.max_tokens <= ops.sample_nucleus_max_history()
+                     or (p.presence_penalty == 0.0
+                         and p.frequency_penalty == 0.0)))
+
+    def _torch_row(self, s: SeqState) -> bool:
+        """Rows left to _sample_torch."""
+        return s.params.needs_torch_sampling and not self._nucleus_row(s)
+
+    def _nuc_plan(self, seqs: list) -> Optional[tuple]:
+        """The rows ops.sample_nucleus serves and its device tensors, or
+        None.  Rows with a penalty get one history slot each, filled from
+        output_ids (every sampled token has landed wherever this is
+        called); cap is the largest max_tokens among them, rounded up to
+        64.  Host->device uploads, as in _cs_plan."""
+        idx = [i for i, s in enumerate(seqs) if self._nucleus_row(s)]
+        if not idx:
+            return None
+        offs, ids, vals, slots, pen = [0], [], [], [], []
+        for i in idx:
+            p = seqs[i].params
+            for t, b in p.logit_bias or ():
+                ids.append(int(t))
+                vals.append(float(b))
+            offs.append(len(ids))
+            if p.presence_penalty != 0.0 or p.frequency_penalty != 0.0:
+                slots.append(len(pen))
+                pen.append(seqs[i])
+            else:
+                slots.append(-1)
+        cap = -(-max([s.params.max_tokens for s in pen] + [1]) // 64) * 64
+        history = torch.zeros((len(pen), cap), dtype=torch.int32)
+        for j, s in enumerate(pen):
+            n = min(len(s.output_ids), cap)
+            history[j, :n] = torch.tensor(s.output_ids[:n], dtype=torch.int32)
+        dev = self.device
+
+        def i32(x):
+            return torch.tensor(x, dtype=torch.int32, device=dev)
+
+        def f32(x):
+            return torch.tensor(x, dtype=torch.float32, device=dev)
+
+        par = [seqs[i].params for i in idx]
+        return (i32(idx), torch.tensor(idx, dtype=torch.long, device=dev),
+                i32([p.top_k for p in par]), f32([p.min_p for p in par]),
+                f32([p.top_p for p in par]),
+                f32([p.presence_penalty for p in par]),
+                f32([p.frequency_penalty for p in par]),
+                i32(offs), i32(ids), f32(vals), i32(slots), history.to(dev),
+                i32([min(len(s.output_ids), cap) for s in pen]))
+
+    @staticmethod
+    def _apply_nucleus(logits: torch.Tensor, plan: tuple,
+                       temps: torch.Tensor, seeds: torch.Tensor, step: int,
+                       toks: torch.Tensor, append: bool) -> torch.Tensor:
+        """_apply_constrained's twin for the nucleus plan.  The slots were
+        built by _nuc_plan, so the op's host-side check of them (a
+        device->host copy) is skipped: nothing here synchronizes."""
+        rows, rows_long = plan[:2]
+        out = ops.sample_nucleus(logits, rows, temps, seeds, step, *plan[2:],
+                                 append, check_slots=False)
+        return toks.index_copy(0, rows_long, out)
 
     @staticmethod
     def _apply_constrained(logits: torch.Tensor, plan: tuple,
@@ -1345,12 +1427,17 @@ class LLMEngine:
         self._b_seeds = torch.tensor([self._seq_seed(s) for s in seqs],
                                      dtype=torch.int64, device=dev)
         self._b_step_off = 0
-        self._b_torch_sampling = any(s.params.needs_torch_sampling for s in seqs)
+        self._b_torch_sampling = any(self._torch_row(s) for s in seqs)
         # requesting rows uploaded once per batch composition, so the
         # decode steps add no host->device copy (= no synchronize)
         self._b_lp_plan = self._lp_plan(seqs)
         # likewise the constrained rows and their static constraints
         self._b_cs_plan = self._cs_plan(seqs)
+        # device_sampling: the top_p / penalty rows and their histories,
+        # which the kernel itself extends until the next rebuild.  A batch
+        # with a torch row samples on the host, which builds its own
+        self._b_nuc_plan = self._nuc_plan(seqs) \
+            if self.device_sampling and not self._b_torch_sampling else None
         # per-row adapter indices (None when no row has an adapter)
         self._b_lora_kw = self._lora_kw([s.adapter for s in seqs])
         self._batch_dirty = False
@@ -1382,14 +1469,20 @@ class LLMEngine:
                 tok_dev = torch.tensor(tokens, dtype=torch.int32,
                                        device=self.device)
                 gr.override_tokens(tok_dev)
-            elif self._b_cs_plan is not None:
+            elif self._b_cs_plan is not None or self._b_nuc_plan is not None:
                 # constrained rows: one device op on the captured logits,
                 # then the same post-replay correction — no host sync.
                 # The graph has already advanced its own seed buffer, so
-                # the op takes the rebuild-time seeds plus the steps since
-                tok_dev = self._apply_constrained(
-                    logits, self._b_cs_plan, self._b_temps, self._b_seeds,
-                    self._b_step_off, tok_dev)
+                # the op takes the rebuild-time seeds plus the steps since.
+                # Nucleus rows (device_sampling) likewise, with their op
+                if self._b_cs_plan is not None:
+                    tok_dev = self._apply_constrained(
+                        logits, self._b_cs_plan, self._b_temps,
+                        self._b_seeds, self._b_step_off, tok_dev)
+                if self._b_nuc_plan is not None:
+                    tok_dev = self._apply_nucleus(
+                        logits, self._b_nuc_plan, self._b_temps,
+                        self._b_seeds, self._b_step_off, tok_dev, append=True)
                 gr.override_tokens(tok_dev)
                 self._b_step_off += 1
             # eager, after the replay and on its logits buffer (stream-
@@ -1422,6 +1515,10 @@ class LLMEngine:
                 tok_dev = self._apply_constrained(
                     logits, self._b_cs_plan, self._b_temps, self._b_seeds,
                     self._b_step_off, tok_dev)
+            if self._b_nuc_plan is not None:
+                tok_dev = self._apply_nucleus(
+                    logits, self._b_nuc_plan, self._b_temps, self._b_seeds,
+                    self._b_step_off, tok_dev, append=True)
             self._b_step_off += 1
         lp = self._compute_logprobs(logits, self._b_lp_plan, tok_dev) \
             if self._b_lp_plan is not None else None

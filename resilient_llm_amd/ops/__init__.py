@@ -224,6 +224,61 @@ def sample_constrained(logits: torch.Tensor, rows: torch.Tensor,
                                   bias_vals)
 
 
+def sample_nucleus_max_history() -> int:
+    """Largest history capacity (tokens per slot) ``sample_nucleus``
+    takes: its LDS count table holds twice as many entries.  The loaded
+    extension's own limit when there is one, else the reference's."""
+    if _loaded:
+        return int(torch.ops.rlli.sample_nucleus_max_history())
+    return ref.NUCLEUS_MAX_HISTORY
+
+
+def sample_nucleus(logits: torch.Tensor, rows: torch.Tensor,
+                   temperatures: torch.Tensor, seeds: torch.Tensor,
+                   step: int, top_k: torch.Tensor, min_p: torch.Tensor,
+                   top_p: torch.Tensor, presence: torch.Tensor,
+                   frequency: torch.Tensor, bias_offsets: torch.Tensor,
+                   bias_ids: torch.Tensor, bias_vals: torch.Tensor,
+                   hist_slot: torch.Tensor, history: torch.Tensor,
+                   hist_len: torch.Tensor, append: bool,
+                   check_slots: bool = True) -> torch.Tensor:
+    """``sample_constrained`` plus nucleus (top_p) filtering and presence /
+    frequency penalties for rows ``rows`` of ``logits`` -> int32 tokens [R].
+
+    ``history`` int32 [n_slots, cap] holds one token history per slot,
+    ``hist_len`` int32 [n_slots] its length; selected row r uses slot
+    ``hist_slot[r]`` (-1: none; slots of one call are distinct).  With
+    c(t) the count of t in that history (ids outside the vocab ignored),
+
+      z(t) = float(logit) - (presence[r] + frequency[r] * c(t)) [c(t) > 0]
+             + bias(t)                       (fp32, in this order)
+
+    Greedy rows (T <= 0) take arg-max z, lowest index on ties.  Sampled
+    rows keep z >= the k-th largest z and z >= z_max + T*ln(min_p) as
+    ``sample_constrained`` does, then the nucleus over the survivors: with
+    w = exp((z - z_max)/T) and W their total weight, t stays iff the
+    weight of survivors with z strictly above z(t) is < top_p[r] * W —
+    the smallest prefix whose mass reaches top_p, with every token equal
+    to the boundary value kept (top_p <= 0 or >= 1 is off).  The draw is
+    ``sample``'s Gumbel-max over what is kept, keyed by (seed, step, index)
+    alike: a row with no penalty and top_p off gets ``sample_constrained``'s
+    token.  With ``append`` the chosen token is stored at
+    ``history[slot, hist_len[slot]]`` and the length grows by one, unless
+    the slot is full.  The logits are not modified.  ``check_slots``
+    validates the ``hist_slot`` values on the host, which synchronizes; a
+    caller that built them itself may pass False."""
+    if logits.is_cuda:
+        _gpu()
+        return torch.ops.rlli.sample_nucleus(
+            logits, rows, temperatures, seeds, step, top_k, min_p, top_p,
+            presence, frequency, bias_offsets, bias_ids, bias_vals,
+            hist_slot, history, hist_len, append, check_slots)
+    return ref.sample_nucleus(logits, rows, temperatures, seeds, step, top_k,
+                              min_p, top_p, presence, frequency,
+                              bias_offsets, bias_ids, bias_vals, hist_slot,
+                              history, hist_len, append)
+
+
 def token_logprobs(logits: torch.Tensor, rows: torch.Tensor,
                    tokens: torch.Tensor, k: int):
     """Log-probability of ``tokens[i]`` under row ``rows[i]`` of the RAW

@@ -758,6 +758,102 @@ Tensor sample_constrained(const Tensor& logits, const Tensor& rows,
   return out;
 }
 
+// ------------------------------------------------------- sample_nucleus
+// rows / bias VALUES are trusted as in sample_constrained.  hist_slot
+// values are checked on the host when check_slots is set (a device->host
+// copy, so a caller that built the slots itself and must not synchronize
+// passes false); the kernel treats a slot outside [0, n_slots) as -1.
+int64_t sample_nucleus_max_history() {
+  return rlli::sample_nucleus_max_history();
+}
+
+Tensor sample_nucleus(const Tensor& logits, const Tensor& rows,
+                      const Tensor& temperatures, const Tensor& seeds,
+                      int64_t step, const Tensor& top_k, const Tensor& min_p,
+                      const Tensor& top_p, const Tensor& presence,
+                      const Tensor& frequency, const Tensor& bias_offsets,
+                      const Tensor& bias_ids, const Tensor& bias_vals,
+                      const Tensor& hist_slot, Tensor& history,
+                      Tensor& hist_len, bool append, bool check_slots) {
+  check_bf16_contig(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(1) >= 1,
+              "logits must be [B, V] with V >= 1");
+  for (const Tensor* t : std::initializer_list<const Tensor*>{
+           &rows, &top_k, &bias_offsets, &bias_ids, &hist_slot, &history,
+           &hist_len}) {
+    TORCH_CHECK(t->scalar_type() == at::kInt && t->is_contiguous() &&
+                t->is_cuda() && t->device() == logits.device(),
+                "rows/top_k/bias_offsets/bias_ids/hist_slot/history/hist_len "
+                "must be contiguous int32 on the logits' device");
+  }
+  for (const Tensor* t : {&temperatures, &min_p, &top_p, &presence,
+                          &frequency, &bias_vals}) {
+    TORCH_CHECK(t->scalar_type() == at::kFloat && t->is_contiguous() &&
+                t->is_cuda() && t->device() == logits.device(),
+                "temperatures/min_p/top_p/presence/frequency/bias_vals must "
+                "be contiguous float32 on the logits' device");
+  }
+  TORCH_CHECK(seeds.scalar_type() == at::kLong && seeds.is_contiguous() &&
+              seeds.is_cuda() && seeds.device() == logits.device(),
+              "seeds must be contiguous int64 on the logits' device");
+  const int64_t batch = logits.size(0);
+  const int64_t vocab = logits.size(1);
+  TORCH_CHECK(temperatures.numel() == batch && seeds.numel() == batch,
+              "temperatures/seeds must have one entry per logits row");
+  const int64_t n_rows = rows.numel();
+  TORCH_CHECK(top_k.numel() == n_rows && min_p.numel() == n_rows &&
+              top_p.numel() == n_rows && presence.numel() == n_rows &&
+              frequency.numel() == n_rows && hist_slot.numel() == n_rows &&
+              bias_offsets.numel() == n_rows + 1,
+              "rows/top_k/min_p/top_p/presence/frequency/hist_slot/"
+              "bias_offsets length mismatch");
+  TORCH_CHECK(bias_ids.numel() == bias_vals.numel(),
+              "bias_ids/bias_vals length mismatch");
+  TORCH_CHECK(bias_ids.numel() < (int64_t(1) << 31), "bias list too long");
+  TORCH_CHECK(vocab <= rlli::sample_constrained_max_vocab(),
+              "sample_nucleus supports vocab <= ",
+              rlli::sample_constrained_max_vocab(), ", got ", vocab);
+  TORCH_CHECK(history.dim() == 2, "history must be [n_slots, cap]");
+  const int64_t n_slots = history.size(0);
+  const int64_t cap = history.size(1);
+  TORCH_CHECK(cap <= rlli::sample_nucleus_max_history(),
+              "sample_nucleus supports a history cap <= ",
+              rlli::sample_nucleus_max_history(), ", got ", cap);
+  TORCH_CHECK(hist_len.numel() == n_slots,
+              "hist_len must have one entry per history slot");
+  TORCH_CHECK(n_slots < (int64_t(1) << 31), "too many history slots");
+  if (check_slots && n_rows > 0) {
+    const Tensor host = hist_slot.cpu();
+    const int32_t* hs = host.data_ptr<int32_t>();
+    std::vector<char> seen(size_t(n_slots), 0);
+    for (int64_t i = 0; i < n_rows; ++i) {
+      TORCH_CHECK(hs[i] >= -1 && hs[i] < n_slots, "hist_slot[", i, "] = ",
+                  hs[i], " is outside [-1, ", n_slots, ")");
+      if (hs[i] < 0) continue;
+      TORCH_CHECK(!seen[size_t(hs[i])], "history slot ", hs[i],
+                  " is given to two selected rows");
+      seen[size_t(hs[i])] = 1;
+    }
+  }
+  Tensor out = at::empty({n_rows}, logits.options().dtype(at::kInt));
+  if (n_rows == 0) return out;
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(logits.device());
+  rlli::launch_sample_nucleus(
+      bf16_ptr(logits), rows.data_ptr<int32_t>(),
+      temperatures.data_ptr<float>(),
+      reinterpret_cast<const uint64_t*>(seeds.data_ptr<int64_t>()),
+      uint64_t(step), top_k.data_ptr<int32_t>(), min_p.data_ptr<float>(),
+      top_p.data_ptr<float>(), presence.data_ptr<float>(),
+      frequency.data_ptr<float>(), bias_offsets.data_ptr<int32_t>(),
+      bias_ids.data_ptr<int32_t>(), bias_vals.data_ptr<float>(),
+      int(bias_ids.numel()), hist_slot.data_ptr<int32_t>(),
+      history.data_ptr<int32_t>(), hist_len.data_ptr<int32_t>(),
+      int(n_slots), int(cap), append, out.data_ptr<int32_t>(), int(n_rows),
+      int(vocab), current_stream(logits));
+  check_launch("sample_nucleus");
+  return out;
+}
+
 // ------------------------------------------------------- token_logprobs
 // rows/tokens VALUES are trusted (as slot_mapping is): rows index
 // logits' first dim, tokens its second.
@@ -949,6 +1045,13 @@ TORCH_LIBRARY(rlli, m) {
   m.def("sample_constrained(Tensor logits, Tensor rows, Tensor temperatures, "
         "Tensor seeds, int step, Tensor top_k, Tensor min_p, "
         "Tensor bias_offsets, Tensor bias_ids, Tensor bias_vals) -> Tensor");
+  m.def("sample_nucleus(Tensor logits, Tensor rows, Tensor temperatures, "
+        "Tensor seeds, int step, Tensor top_k, Tensor min_p, Tensor top_p, "
+        "Tensor presence, Tensor frequency, Tensor bias_offsets, "
+        "Tensor bias_ids, Tensor bias_vals, Tensor hist_slot, "
+        "Tensor(a!) history, Tensor(b!) hist_len, bool append, "
+        "bool check_slots) -> Tensor");
+  m.def("sample_nucleus_max_history() -> int", &sample_nucleus_max_history);
   m.def("token_logprobs(Tensor logits, Tensor rows, Tensor tokens, int k) "
         "-> (Tensor, Tensor, Tensor)");
   m.def("skinny_linear(Tensor x, Tensor w) -> Tensor");
@@ -986,6 +1089,7 @@ TORCH_LIBRARY_IMPL(rlli, CUDA, m) {
   m.impl("prefill_attn", &prefill_attn);
   m.impl("sample", &sample);
   m.impl("sample_constrained", &sample_constrained);
+  m.impl("sample_nucleus", &sample_nucleus);
   m.impl("token_logprobs", &token_logprobs);
   m.impl("skinny_linear", &skinny_linear);
   m.impl("skinny2_linear", &skinny2_linear);

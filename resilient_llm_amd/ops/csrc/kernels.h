@@ -183,6 +183,38 @@ void launch_sample_constrained(
     int32_t* out_tokens,               // [n_rows]
     int n_rows, int vocab, hipStream_t stream);
 
+// sample_constrained plus nucleus (top_p) filtering and presence/frequency
+// penalties: z = float(logit) - (presence + frequency * c) [c > 0] + bias,
+// c counted from the row's slot of a device-resident token history; the
+// top_k / min_p floor on z, then keep a survivor iff the softmax(z/T)
+// mass of the survivors strictly above it is < top_p * their total (ties
+// at the cut stay; top_p <= 0 or >= 1: off).  hist_slot[r] == -1: no
+// history.  With `append` the chosen token is stored at the end of the
+// row's slot (slots of one launch are distinct).  The logits are only
+// read; no workspace (sampling_nucleus.hip).
+int sample_nucleus_max_history();
+void launch_sample_nucleus(
+    const uint16_t* logits,            // [batch, vocab] bf16
+    const int32_t* rows,               // [n_rows] row indices into logits
+    const float* temperatures,         // [batch]
+    const uint64_t* seeds,             // [batch]
+    uint64_t step,
+    const int32_t* top_k,              // [n_rows]
+    const float* min_p,                // [n_rows]
+    const float* top_p,                // [n_rows]
+    const float* presence,             // [n_rows]
+    const float* frequency,            // [n_rows]
+    const int32_t* bias_offsets,       // [n_rows + 1]
+    const int32_t* bias_ids,           // [n_bias_total]
+    const float* bias_vals,            // [n_bias_total]
+    int n_bias_total,
+    const int32_t* hist_slot,          // [n_rows], -1 or a slot
+    int32_t* history,                  // [n_slots, cap]
+    int32_t* hist_len,                 // [n_slots]
+    int n_slots, int cap, bool append,
+    int32_t* out_tokens,               // [n_rows]
+    int n_rows, int vocab, hipStream_t stream);
+
 // Fused log-softmax value of one emitted token per selected row plus the
 // row's k most likely tokens (value descending, index ascending on ties),
 // computed on the RAW logits — one pass over the selected rows, nothing

@@ -217,6 +217,99 @@ def sample_constrained(logits: torch.Tensor, rows: torch.Tensor,
     return out
 
 
+NUCLEUS_MAX_HISTORY = 4096     # kNucMaxHistory of sampling_nucleus.hip
+
+
+def sample_nucleus(logits: torch.Tensor, rows: torch.Tensor,
+                   temperatures: torch.Tensor, seeds: torch.Tensor,
+                   step: int, top_k: torch.Tensor, min_p: torch.Tensor,
+                   top_p: torch.Tensor, presence: torch.Tensor,
+                   frequency: torch.Tensor, bias_offsets: torch.Tensor,
+                   bias_ids: torch.Tensor, bias_vals: torch.Tensor,
+                   hist_slot: torch.Tensor, history: torch.Tensor,
+                   hist_len: torch.Tensor, append: bool) -> torch.Tensor:
+    """``sample_constrained`` plus penalties and the nucleus.  z =
+    float(logit) - (presence + frequency * c) [c > 0] + bias in fp32, c
+    counted from the row's history slot; the top_k / min_p floor; then a
+    survivor stays iff the weight exp((z - z_max)/T) of the survivors
+    strictly above it is < top_p * their total (ties at the cut all stay;
+    top_p <= 0 or >= 1 off).  Greedy rows are exact; stochastic rows draw
+    from the renormalised kept set with a torch generator seeded per row
+    from (seeds[rows[r]], step) exactly as ``sample_constrained`` does —
+    the kernel's reproducibility contract, not its stream.  ``append``
+    stores the chosen token at the end of the row's slot unless full."""
+    R = rows.numel()
+    if not (top_k.numel() == R and min_p.numel() == R and top_p.numel() == R
+            and presence.numel() == R and frequency.numel() == R
+            and hist_slot.numel() == R and bias_offsets.numel() == R + 1):
+        raise ValueError("rows/top_k/min_p/top_p/presence/frequency/"
+                         "hist_slot/bias_offsets length mismatch")
+    if bias_ids.numel() != bias_vals.numel():
+        raise ValueError("bias_ids/bias_vals length mismatch")
+    if history.dim() != 2 or hist_len.numel() != history.shape[0]:
+        raise ValueError("history must be [n_slots, cap] with one hist_len "
+                         "entry per slot")
+    n_slots, cap = history.shape
+    if cap > NUCLEUS_MAX_HISTORY:
+        raise ValueError(f"history cap must be <= {NUCLEUS_MAX_HISTORY}, "
+                         f"got {cap}")
+    slots = hist_slot.tolist()
+    used = [s for s in slots if s >= 0]
+    if any(s < -1 or s >= n_slots for s in slots) \
+            or len(set(used)) != len(used):
+        raise ValueError("hist_slot values must be -1 or distinct slots")
+    V = logits.shape[1]
+    out = torch.empty(R, dtype=torch.int32, device=logits.device)
+    offs = bias_offsets.tolist()
+    C = 0x9e3779b97f4a7c15
+    for r, row in enumerate(rows.tolist()):
+        z = logits[row].float().clone()
+        slot = slots[r]
+        n = min(max(int(hist_len[slot]), 0), cap) if slot >= 0 else 0
+        pres, freq = presence[r].float(), frequency[r].float()
+        if n > 0 and (float(pres) != 0.0 or float(freq) != 0.0):
+            h = history[slot, :n].long()
+            ids, c = torch.unique(h[(h >= 0) & (h < V)], return_counts=True)
+            z[ids] -= pres + freq * c.float()
+        b0, b1 = offs[r], offs[r + 1]
+        if b1 > b0:
+            z[bias_ids[b0:b1].long()] += bias_vals[b0:b1].float()
+        T = float(temperatures[row])
+        if T <= 0:
+            tok = int(z.argmax())
+        else:
+            keep = torch.ones(V, dtype=torch.bool, device=z.device)
+            k = int(top_k[r])
+            if 1 <= k < V:
+                keep &= z >= z.topk(k).values[-1]
+            m = float(min_p[r])
+            if m > 0:
+                keep &= z >= z.max() + torch.tensor(T, dtype=torch.float32) \
+                    * torch.log(torch.tensor(m, dtype=torch.float32))
+            p = float(top_p[r])
+            if 0.0 < p < 1.0:
+                w = torch.where(keep, torch.exp((z - z.max()).double() / T),
+                                z.new_zeros((), dtype=torch.float64))
+                vals, inv = torch.unique(z, return_inverse=True)  # ascending
+                per_val = torch.zeros(vals.numel(), dtype=torch.float64,
+                                      device=z.device).index_add_(0, inv, w)
+                # weight strictly above each distinct value
+                above = per_val.flip(0).cumsum(0).flip(0) - per_val
+                keep &= above[inv] < p * w.sum()
+            probs = torch.softmax(
+                torch.where(keep, z, z.new_tensor(float("-inf"))) / T, dim=-1)
+            gen = torch.Generator(device=logits.device)
+            gen.manual_seed((int(seeds[row]) + C * step) & 0x7fffffffffffffff)
+            tok = int(torch.multinomial(probs, 1, generator=gen))
+        out[r] = tok
+        if append and slot >= 0:
+            n_raw = int(hist_len[slot])
+            if 0 <= n_raw < cap:
+                history[slot, n_raw] = tok
+                hist_len[slot] = n_raw + 1
+    return out
+
+
 def token_logprobs(logits: torch.Tensor, rows: torch.Tensor,
                    tokens: torch.Tensor, k: int):
     """Log-softmax (fp32, RAW logits — independent of temperature, top-p

@@ -80,6 +80,7 @@ class EngineWorker(Worker):
                  kv_dtype: str = "bf16",
                  quant=None,
                  spec_lookup: int = 0,
+                 device_sampling: bool = False,
                  adapters: Optional[dict] = None,
                  seed: int = 0) -> None:
         super().__init__(device=device_label or f"gpu:{device}",
@@ -143,7 +144,8 @@ class EngineWorker(Worker):
                                 # lockstep, like admission_window_s
                                 target_step_ms=None if tp_control is not None
                                 else target_step_ms,
-                                spec_lookup=spec_lookup)
+                                spec_lookup=spec_lookup,
+                                device_sampling=device_sampling)
         if use_graphs and torch_device != "cpu":
             from ..engine.graph import install_graph_runner
             install_graph_runner(self.engine)

@@ -36,6 +36,7 @@ def spawn_gpu_worker(device_index: str, model_name: str,
                      kv_dtype: str | None = None,
                      quant: str | None = None,
                      spec_lookup: int | None = None,
+                     device_sampling: bool = False,
                      adapters: dict | None = None,
                      extra_env: dict | None = None) -> subprocess.Popen:
     """``device_index`` may be a sub-device replica like ``0.1``: several
@@ -67,6 +68,8 @@ def spawn_gpu_worker(device_index: str, model_name: str,
         cmd += ["--quant", str(quant)]
     if spec_lookup:
         cmd += ["--spec-lookup", str(spec_lookup)]
+    if device_sampling:
+        cmd.append("--device-sampling")
     for name, path in (adapters or {}).items():
         cmd += ["--adapter", f"{name}={path}"]
     return subprocess.Popen(cmd, env=env)
@@ -120,6 +123,7 @@ def register_gpu_workers(config: Config, registry: WorkerRegistry,
         kv_dtype = extra.get("kv_dtype")
         quant = extra.get("quantization")
         spec = extra.get("spec_lookup")
+        dev_sampling = bool(extra.get("device_sampling"))
         # every alias on this worker may declare adapters: the union loads
         adapters = config.worker_adapters("gpu", target)
         eos = extra.get("eos_id")
@@ -130,17 +134,19 @@ def register_gpu_workers(config: Config, registry: WorkerRegistry,
                                 weights=weights, eos_ids=eos_list,
                                 kv_dtype=kv_dtype, quant=quant,
                                 spec_lookup=spec, adapters=adapters,
+                                device_sampling=dev_sampling,
                                 target_step_ms=slo)
         client = RpcWorkerClient(f"gpu:{target}", {model_name}, sock)
         client.proc = proc
         client.respawn = (lambda t=target, m=model_name, s=sock,
-                          adapters=adapters:
+                          adapters=adapters, dev_sampling=dev_sampling:
                           spawn_gpu_worker(t, m, s, kv_gb=kv_gb,
                                            max_batch=max_batch,
                                            use_graphs=use_graphs,
                                            weights=weights, eos_ids=eos_list,
                                            kv_dtype=kv_dtype, quant=quant,
                                            spec_lookup=spec,
+                                           device_sampling=dev_sampling,
                                            adapters=adapters,
                                            target_step_ms=slo))
         registry.register("gpu", target, client)

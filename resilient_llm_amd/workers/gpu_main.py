@@ -29,6 +29,10 @@ def main() -> None:
     ap.add_argument("--spec-lookup", type=int, default=0,
                     help="prompt-lookup speculative decoding depth "
                          "(greedy requests; 0 = off)")
+    ap.add_argument("--device-sampling", action="store_true",
+                    help="serve top_p and presence/frequency penalties "
+                         "with the fused device sampler instead of the "
+                         "host torch path")
     ap.add_argument("--quant", default=None, choices=(None, "fp8", "int4"),
                     help="fp8: W8A8-fp8 weights for gate_up/down/lm_head "
                          "(rowwise scaled_mm); int4: W4A16 group-128 "
@@ -73,6 +77,7 @@ def main() -> None:
                               kv_dtype=args.kv_dtype,
                               quant=args.quant,
                               spec_lookup=args.spec_lookup,
+                              device_sampling=args.device_sampling,
                               adapters=dict(a.split("=", 1)
                                             for a in args.adapter or ()),
                               target_step_ms=args.target_step_ms)
