@@ -193,6 +193,24 @@ def _parse_deployment(entry: Any, idx: int) -> Deployment:
         _require(kind != "pool",
                  f"model_list[{idx}].litellm_params.device_sampling is "
                  f"served by gpu/<device> workers only, not by {model!r}")
+    if "shared_prefix_attention" in extra:
+        _require(isinstance(extra["shared_prefix_attention"], bool),
+                 f"model_list[{idx}].litellm_params.shared_prefix_attention "
+                 f"must be a bool, got {extra['shared_prefix_attention']!r}")
+        # the kernels read a bf16 cache only
+        _require(not extra["shared_prefix_attention"]
+                 or extra.get("kv_dtype", "bf16") != "fp8",
+                 f"model_list[{idx}].litellm_params.shared_prefix_attention "
+                 f"needs a bf16 KV cache, not kv_dtype: fp8")
+        # the TP lockstep op stream does not carry the plan
+        _require(kind != "pool",
+                 f"model_list[{idx}].litellm_params.shared_prefix_attention "
+                 f"is served by gpu/<device> workers only, not by {model!r}")
+    if "shared_prefix_min_tokens" in extra:
+        v = extra["shared_prefix_min_tokens"]
+        _require(isinstance(v, int) and not isinstance(v, bool) and v >= 16,
+                 f"model_list[{idx}].litellm_params.shared_prefix_min_tokens "
+                 f"must be an int >= 16 (one KV block), got {v!r}")
     # LoRA: ``adapters`` {name: PEFT directory} loads on the worker at
     # start, ``adapter`` names the one this deployment serves
     if "adapters" in extra:

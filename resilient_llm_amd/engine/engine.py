@@ -23,7 +23,7 @@ from typing import Optional
 import torch
 
 from .. import ops
-from .kv_cache import PagedKVCache, block_hash_chain
+from .kv_cache import PagedKVCache, block_hash_chain, shared_prefix_groups
 
 # roctx phase markers for rocprofv3 --marker-trace:
 # torch.cuda.nvtx lowers to roctx on ROCm.  Opt-in: RLLI_ROCTX=1.
@@ -134,6 +134,8 @@ class LLMEngine:
                  eos_ids=None,
                  spec_lookup: int = 0,
                  device_sampling: bool = False,
+                 shared_prefix_attention: bool = False,
+                 shared_prefix_min_tokens: int = 1024,
                  seed: int = 0) -> None:
         self.model = model
         self.kv = kv_cache
@@ -185,6 +187,29 @@ class LLMEngine:
         # draws by Gumbel-max like every other device row: same
         # distribution as the default mode, a different stream per seed
         self.device_sampling = device_sampling
+        # opt-in: decode rows that share >= shared_prefix_min_tokens of
+        # leading physical KV blocks (n > 1 choices, prefix-cache hits)
+        # read them once per group (ops.decode_attn_shared_qkv).  Such a
+        # batch decodes eagerly; the default threshold is the graph
+        # runner's envelope (64 blocks x 16 tokens), beyond which a batch
+        # is eager anyway — a lower one trades the replay for the shared
+        # read
+        self.shared_prefix_attention = shared_prefix_attention
+        self.shared_prefix_min_tokens = int(shared_prefix_min_tokens)
+        self._shared_group = 0
+        if shared_prefix_attention:
+            if self.shared_prefix_min_tokens < kv_cache.block_size:
+                raise ValueError("shared_prefix_min_tokens must be at least "
+                                 "one KV block")
+            self._shared_group = model.n_heads // model.n_kv_heads
+            if self.device.type == "cuda" and not (
+                    self._shared_group in (4, 8)
+                    and kv_cache.block_size == 16
+                    and kv_cache.head_dim == 128
+                    and kv_cache.k.dtype == torch.bfloat16):
+                raise ValueError(
+                    "shared_prefix_attention needs a bf16 KV cache, block "
+                    "size 16, head_dim 128 and a GQA group of 4 or 8")
         self._prefill_budget = max_prefill_tokens
         self._budget_floor = min(max_prefill_tokens, 256)
         self.step_count = 0
@@ -222,6 +247,9 @@ class LLMEngine:
                       # n > 1 groups: sequences forked off a leader, and
                       # the prompt blocks they share instead of owning
                       "forks": 0, "fork_shared_blocks": 0,
+                      # shared_prefix_attention: decode steps that ran
+                      # with a plan, and their rows that were in a group
+                      "shared_prefix_steps": 0, "shared_prefix_rows": 0,
                       "admit_events": []}
         # decode graph runner installed by engine/graph.py (GPU only)
         self.graph_runner = None
@@ -1440,8 +1468,42 @@ class LLMEngine:
             if self.device_sampling and not self._b_torch_sampling else None
         # per-row adapter indices (None when no row has an adapter)
         self._b_lora_kw = self._lora_kw([s.adapter for s in seqs])
+        self._b_shared_plan = self._shared_plan(seqs) \
+            if self.shared_prefix_attention else None
         self._batch_dirty = False
         self._graph_loaded = False
+
+    def _shared_plan(self, seqs: list) -> Optional[tuple]:
+        """The device plan of ops.decode_attn_shared_qkv for this batch
+        (rows grouped by kv_cache.shared_prefix_groups), its workspace
+        included, and the number of grouped rows — or None when no group
+        forms.  Shared blocks are full prompt blocks nobody writes again,
+        and n_cached only grows, so the plan holds until the composition
+        changes.  Host->device uploads, as in _cs_plan."""
+        group = self._shared_group
+        mpt = 64 // group if group in (4, 8) else 16
+        host = shared_prefix_groups(
+            [s.blocks for s in seqs], [s.n_cached for s in seqs],
+            self.block_size, self.shared_prefix_min_tokens, mpt)
+        if host is None:
+            return None
+        dev = self.device
+        T = len(host["tile_blocks"])
+        n_kv = self.kv.n_kv_heads
+        if dev.type == "cuda":
+            kv_tiles = -(-max(host["tile_blocks"]) * self.block_size // 64)
+            chunks = ops.shared_prefix_chunks(T, n_kv, kv_tiles)
+        else:
+            chunks = 0                # the CPU reference takes no workspace
+        plan = tuple(
+            torch.tensor(host[k], dtype=torch.int32, device=dev)
+            for k in ("n_shared", "row_tile", "row_slot", "tile_rows",
+                      "tile_blocks", "tile_bt_row")) + (
+            torch.empty((T, n_kv, chunks, 64, self.kv.head_dim),
+                        dtype=torch.float32, device=dev),
+            torch.empty((T, n_kv, chunks, 64, 2), dtype=torch.float32,
+                        device=dev))
+        return plan, sum(1 for n in host["n_shared"] if n)
 
     def _decode_step(self) -> list[StepOutput]:
         seqs = self.running
@@ -1449,8 +1511,10 @@ class LLMEngine:
             self._rebuild_batch()
         gr = self.graph_runner
         # a batch with an adapter row takes the eager branch: the captured
-        # graph holds the base model's launches only
+        # graph holds the base model's launches only; so does a batch with
+        # a shared-prefix plan, whose attention is another op
         if (gr is not None and not self._b_lora_kw
+                and self._b_shared_plan is None
                 and gr.steady_ok(len(seqs), self._b_bt.shape[1])):
             # steady path: the WHOLE step (slots, forward, sample, state
             # advance) is one graph replay; the static buffers are loaded
@@ -1501,9 +1565,14 @@ class LLMEngine:
         slots = bt.gather(1, block_idx.unsqueeze(1)).squeeze(1) \
             * self.block_size + (pos - block_idx.int() * self.block_size)
         seq_lens = pos + 1
+        shared_kw = {}
+        if self._b_shared_plan is not None:
+            shared_kw["shared_plan"], n_rows = self._b_shared_plan
+            self.stats["shared_prefix_steps"] += 1
+            self.stats["shared_prefix_rows"] += n_rows
         logits = self.model.forward_decode(self._b_ids, pos, self.kv,
                                            slots, bt, seq_lens,
-                                           **self._b_lora_kw)
+                                           **self._b_lora_kw, **shared_kw)
         if self._b_torch_sampling:
             tokens = self._sample(logits, seqs)     # torch top-p path (sync)
             tok_dev = torch.tensor(tokens, dtype=torch.int32,

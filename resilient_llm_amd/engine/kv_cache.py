@@ -43,6 +43,58 @@ def block_hash_chain(token_ids, block_size: int,
     return keys
 
 
+def shared_prefix_groups(block_lists, n_cached, block_size: int,
+                         min_tokens: int, members_per_tile: int):
+    """Host plan for ``ops.decode_attn_shared_qkv``: which rows of a decode
+    batch share a leading run of physical KV blocks.
+
+    Rows are bucketed by their first block id.  In a bucket of >= 2 rows
+    the shared length is the longest common prefix of the members' block
+    lists, clamped to ``min(n_cached) // block_size`` blocks so that a
+    shared block is full for every member; the bucket is a group when that
+    is >= ``min_tokens`` tokens.  One level only: members that share more
+    than their whole bucket are not split out.  A group of more than
+    ``members_per_tile`` rows spans several tiles.
+
+    Returns None when no group forms, else a dict of lists: per row
+    ``n_shared`` (tokens; 0 = in no group), ``row_tile``, ``row_slot``;
+    per tile ``tile_rows`` (member rows, -1 padded), ``tile_blocks``,
+    ``tile_bt_row`` (a member whose block list names the shared blocks)."""
+    buckets: dict = {}
+    for row, blocks in enumerate(block_lists):
+        if blocks:
+            buckets.setdefault(blocks[0], []).append(row)
+    B = len(block_lists)
+    plan = {"n_shared": [0] * B, "row_tile": [-1] * B, "row_slot": [0] * B,
+            "tile_rows": [], "tile_blocks": [], "tile_bt_row": []}
+    for rows in buckets.values():
+        if len(rows) < 2:
+            continue
+        first = block_lists[rows[0]]
+        n = min(min(n_cached[r] for r in rows) // block_size,
+                min(len(block_lists[r]) for r in rows))
+        for r in rows[1:]:
+            other = block_lists[r]
+            k = 0
+            while k < n and other[k] == first[k]:
+                k += 1
+            n = k
+        if n == 0 or n * block_size < min_tokens:
+            continue
+        for i in range(0, len(rows), members_per_tile):
+            members = rows[i:i + members_per_tile]
+            tile = len(plan["tile_blocks"])
+            for slot, r in enumerate(members):
+                plan["n_shared"][r] = n * block_size
+                plan["row_tile"][r] = tile
+                plan["row_slot"][r] = slot
+            plan["tile_rows"].append(
+                members + [-1] * (members_per_tile - len(members)))
+            plan["tile_blocks"].append(n)
+            plan["tile_bt_row"].append(members[0])
+    return plan if plan["tile_blocks"] else None
+
+
 class PagedKVCache:
     def __init__(self, n_layers: int, num_blocks: int, n_kv_heads: int,
                  block_size: int, head_dim: int, device="cpu",

@@ -703,10 +703,20 @@ class LlamaForCausalLM:
                        kv_cache, slot_mapping: torch.Tensor,
                        block_tables: torch.Tensor,
                        seq_lens: torch.Tensor,
-                       adapter_idx: Optional[torch.Tensor] = None
+                       adapter_idx: Optional[torch.Tensor] = None,
+                       shared_plan: Optional[tuple] = None
                        ) -> torch.Tensor:
-        """One token per sequence; returns [batch, vocab] logits."""
+        """One token per sequence; returns [batch, vocab] logits.  With a
+        ``shared_plan`` (ops.decode_attn_shared_qkv) rows that share
+        leading KV blocks read them once per group; the plan's workspace
+        serves every layer."""
         def attn(i, qkv, k_cache, v_cache):
+            if shared_plan is not None:
+                ops.rope_kv_append_qkv_(qkv, positions, self.cos_sin, k_cache,
+                                        v_cache, slot_mapping, self.n_heads)
+                return ops.decode_attn_shared_qkv(
+                    qkv, k_cache, v_cache, block_tables, seq_lens,
+                    shared_plan, self.scale, self.n_heads)
             return ops.decode_attn_rope_qkv(
                 qkv, positions, self.cos_sin, k_cache, v_cache, slot_mapping,
                 block_tables, seq_lens, self.scale, self.n_heads)

@@ -157,6 +157,39 @@ def decode_attn_rope_qkv(qkv, positions, cos_sin, k_cache, v_cache,
                            scale, n_q)
 
 
+def shared_prefix_chunks(tiles: int, n_kv: int, kv_tiles: int) -> int:
+    """Chunks of the shared prefix per (row tile, kv-head) that fill the
+    device: what a ``decode_attn_shared_qkv`` plan's workspace is sized
+    with when the longest prefix spans ``kv_tiles`` 64-token tiles."""
+    _gpu()
+    return int(torch.ops.rlli.shared_prefix_chunks(tiles, n_kv, kv_tiles))
+
+
+def decode_attn_shared_qkv(qkv: torch.Tensor, k_cache: torch.Tensor,
+                           v_cache: torch.Tensor, block_table: torch.Tensor,
+                           seq_lens: torch.Tensor, plan, scale: float,
+                           n_q: int) -> torch.Tensor:
+    """``decode_attn_qkv`` for a batch whose rows share leading physical
+    KV blocks: each group's shared run is read once (MFMA, f32 partials
+    into the plan's workspace), then every row walks its private blocks
+    and folds its partials in.  ``plan`` = (n_shared [B] shared tokens
+    per row, 0 = in no group; row_tile [B]; row_slot [B]; tile_rows
+    [T, 64/GROUP] member rows, -1 padded; tile_blocks [T]; tile_bt_row
+    [T]; ws_acc [T, n_kv, chunks, 64, D] f32; ws_ml [T, n_kv, chunks, 64,
+    2] f32) — int32 device tensors from ``engine.kv_cache`` plus the
+    workspace, whose third dimension is the chunk count the call runs
+    with.  bf16 cache, block size 16, head_dim 128, GQA group 4 or 8.
+    Mathematically ``decode_attn_qkv``; P is rounded to bf16 in the
+    shared phase.  On CPU tensors it is ``decode_attn_qkv``."""
+    if qkv.is_cuda:
+        _gpu()
+        return torch.ops.rlli.decode_attn_shared_qkv(
+            qkv, k_cache, v_cache, block_table, seq_lens, list(plan), scale,
+            n_q)
+    return decode_attn_qkv(qkv, k_cache, v_cache, block_table, seq_lens,
+                           scale, n_q)
+
+
 def prefill_attn_qkv(qkv: torch.Tensor, cu_seqlens: torch.Tensor,
                      scale: float, n_q: int, n_kv: int,
                      head_dim: int) -> torch.Tensor:

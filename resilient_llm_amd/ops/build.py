@@ -37,6 +37,7 @@ SOURCES = [
     "silu_mul.hip",
     "rope_kv.hip",
     "decode_attn.hip",
+    "decode_attn_shared.hip",
     "prefill_attn.hip",
     "prefill_mfma.hip",
     "sampling.hip",
@@ -56,9 +57,10 @@ HEADERS = ["common.h", "kernels.h", "sampling_common.h"]
 # the flag today, and no wrong result was ever seen without it.  The flag
 # is per source because it does move the code of kernels written before
 # it (sampling.hip's among them), which are left to compile as they did.
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
-    "sampling_nucleus.hip": ["-Xclang", "-target-feature",
-                             "-Xclang", "-packed-fp32-ops"],
+    "sampling_nucleus.hip": _NO_PK_F32,
+    "decode_attn_shared.hip": _NO_PK_F32,
 }
 
 

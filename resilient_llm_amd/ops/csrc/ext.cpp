@@ -367,6 +367,87 @@ Tensor decode_attn_rope_qkv(const Tensor& qkv, const Tensor& positions,
   return out;
 }
 
+// ------------------------------------------------- decode_attn_shared
+// Introspection, as decode_attn_split: the chunk count a plan of `tiles`
+// row tiles is sized with when its longest prefix spans kv_tiles 64-token
+// tiles.  The op itself takes the count from the workspace's shape.
+int64_t shared_prefix_chunks(int64_t tiles, int64_t n_kv, int64_t kv_tiles) {
+  TORCH_CHECK(tiles >= 1 && n_kv >= 1 && kv_tiles >= 1 &&
+              tiles * n_kv < (int64_t(1) << 24) &&
+              kv_tiles < (int64_t(1) << 24), "bad tiles/n_kv/kv_tiles");
+  return rlli::shared_prefix_n_chunks(int(tiles), int(n_kv), int(kv_tiles));
+}
+
+// Shared-prefix decode attention.  plan = (n_shared[B], row_tile[B],
+// row_slot[B], tile_rows[T, 64/GROUP], tile_blocks[T], tile_bt_row[T],
+// ws_acc[T, n_kv, C, 64, D] f32, ws_ml[T, n_kv, C, 64, 2] f32); the plan's
+// VALUES are the caller's contract (engine/kv_cache.py builds them).
+Tensor decode_attn_shared_qkv(const Tensor& qkv, const Tensor& k_cache,
+                              const Tensor& v_cache,
+                              const Tensor& block_table,
+                              const Tensor& seq_lens, at::TensorList plan,
+                              double scale, int64_t n_q) {
+  check_bf16_contig(qkv, "qkv");
+  const bool cache_fp8 = check_cache(k_cache, v_cache);
+  TORCH_CHECK(!cache_fp8, "decode_attn_shared_qkv: kv cache must be bf16");
+  TORCH_CHECK(block_table.scalar_type() == at::kInt && block_table.is_contiguous());
+  TORCH_CHECK(seq_lens.scalar_type() == at::kInt && seq_lens.is_contiguous());
+  const int64_t batch = qkv.size(0);
+  const int64_t n_kv = k_cache.size(1);
+  const int64_t D = k_cache.size(3);
+  const int64_t block_size = k_cache.size(2);
+  TORCH_CHECK(block_size == 16, "block_size must be 16, got ", block_size);
+  TORCH_CHECK(D == 128, "head_dim must be 128, got ", D);
+  TORCH_CHECK(qkv.size(1) == (n_q + 2 * n_kv) * D, "qkv width mismatch");
+  const int64_t group = n_q / n_kv;
+  TORCH_CHECK(n_q % n_kv == 0 && (group == 4 || group == 8),
+              "GQA group must be 4/8, got ", group);
+  TORCH_CHECK(v_cache.sizes() == k_cache.sizes());
+  TORCH_CHECK(block_table.dim() == 2 && block_table.size(0) == batch &&
+              seq_lens.numel() == batch, "block_table/seq_lens batch mismatch");
+  TORCH_CHECK(plan.size() == 8, "plan holds 8 tensors, got ", plan.size());
+  for (size_t i = 0; i < 8; ++i)
+    TORCH_CHECK(plan[i].is_contiguous() && plan[i].device() == qkv.device() &&
+                plan[i].scalar_type() == (i < 6 ? at::kInt : at::kFloat),
+                "plan tensors must be contiguous int32 (workspace: f32) on "
+                "the data's device");
+  const int64_t T = plan[4].numel();
+  const int64_t mpt = 64 / group;
+  TORCH_CHECK(plan[0].numel() == batch && plan[1].numel() == batch &&
+              plan[2].numel() == batch,
+              "plan rows disagree with the batch: ", plan[0].numel(), " vs ",
+              batch);
+  TORCH_CHECK(T >= 1 && plan[5].numel() == T && plan[3].dim() == 2 &&
+              plan[3].size(0) == T && plan[3].size(1) == mpt,
+              "plan tiles must be [T, ", mpt, "] with T >= 1");
+  const Tensor& ws_acc = plan[6];
+  const Tensor& ws_ml = plan[7];
+  TORCH_CHECK(ws_acc.dim() == 5 && ws_acc.size(0) == T &&
+              ws_acc.size(1) == n_kv && ws_acc.size(3) == 64 &&
+              ws_acc.size(4) == D && ws_acc.size(2) >= 1 &&
+              ws_acc.size(2) <= 64 && ws_ml.dim() == 5 &&
+              ws_ml.size(0) == T && ws_ml.size(1) == n_kv &&
+              ws_ml.size(2) == ws_acc.size(2) && ws_ml.size(3) == 64 &&
+              ws_ml.size(4) == 2,
+              "plan workspace must be [T, n_kv, chunks <= 64, 64, head_dim] "
+              "and [.., 64, 2]");
+  TORCH_CHECK(batch * n_kv <= INT32_MAX && T <= INT32_MAX && n_kv <= 65535);
+  Tensor out = at::empty({batch, n_q * D}, qkv.options());
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(qkv.device());
+  rlli::launch_decode_attn_shared(
+      bf16_ptr(qkv), bf16_ptr(k_cache), bf16_ptr(v_cache),
+      block_table.data_ptr<int32_t>(), seq_lens.data_ptr<int32_t>(),
+      plan[0].data_ptr<int32_t>(), plan[1].data_ptr<int32_t>(),
+      plan[2].data_ptr<int32_t>(), plan[3].data_ptr<int32_t>(),
+      plan[4].data_ptr<int32_t>(), plan[5].data_ptr<int32_t>(),
+      ws_acc.data_ptr<float>(), ws_ml.data_ptr<float>(), bf16_ptr(out),
+      int(batch), int(T), int(ws_acc.size(2)), int(n_q), int(n_kv),
+      int(block_table.size(1)), float(scale), int(qkv.size(1)),
+      current_stream(qkv));
+  check_launch("decode_attn_shared_qkv");
+  return out;
+}
+
 // --------------------------------------------------------- prefill_attn
 Tensor prefill_attn(const Tensor& q, const Tensor& k, const Tensor& v,
                     const Tensor& cu_seqlens, double scale) {
@@ -1034,6 +1115,11 @@ TORCH_LIBRARY(rlli, m) {
         "int n_q) -> ()");
   m.def("decode_attn_qkv(Tensor qkv, Tensor k_cache, Tensor v_cache, "
         "Tensor block_table, Tensor seq_lens, float scale, int n_q) -> Tensor");
+  m.def("decode_attn_shared_qkv(Tensor qkv, Tensor k_cache, Tensor v_cache, "
+        "Tensor block_table, Tensor seq_lens, Tensor[] plan, float scale, "
+        "int n_q) -> Tensor");
+  m.def("shared_prefix_chunks(int tiles, int n_kv, int kv_tiles) -> int",
+        &shared_prefix_chunks);
   m.def("decode_attn_rope_qkv(Tensor qkv, Tensor positions, Tensor cos_sin, "
         "Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor slot_mapping, "
         "Tensor block_table, Tensor seq_lens, float scale, int n_q) -> Tensor");
@@ -1085,6 +1171,7 @@ TORCH_LIBRARY_IMPL(rlli, CUDA, m) {
   m.impl("rope_kv_append_qkv_", &rope_kv_append_qkv_);
   m.impl("decode_attn_qkv", &decode_attn_qkv);
   m.impl("decode_attn_rope_qkv", &decode_attn_rope_qkv);
+  m.impl("decode_attn_shared_qkv", &decode_attn_shared_qkv);
   m.impl("prefill_attn_qkv", &prefill_attn_qkv);
   m.impl("prefill_attn", &prefill_attn);
   m.impl("sample", &sample);

@@ -78,6 +78,31 @@ void launch_decode_attn_fused(
     float scale, int qkv_stride, int n_split, float* part_out,
     float* part_ml, bool cache_fp8, hipStream_t stream);
 
+// Shared-prefix decode attention (decode_attn_shared.hip): rows that share
+// a leading run of physical KV blocks read it once per group (MFMA prefix
+// phase into f32 partials), then every row walks its private blocks and
+// folds its partials in.  bf16 cache, block size 16, head_dim 128, GQA
+// group 4 or 8; q is read from the fused qkv rows.
+//   n_shared[batch]      shared tokens of the row (a multiple of 16; 0 =
+//                        in no group: a complete attention, no split-K)
+//   row_tile / row_slot  the row's tile and member slot (unused at 0)
+//   tile_rows[T, 64/G]   member batch rows of a tile, -1 padded
+//   tile_blocks[T]       shared blocks of the tile's group
+//   tile_bt_row[T]       a member row whose block table lists them
+//   ws_acc / ws_ml       [T, n_kv, n_chunks, 64, head_dim] / [.., 64, 2]
+// shared_prefix_n_chunks: the chunk count that fills the device, for
+// `tiles` row tiles whose longest prefix spans kv_tiles 64-token tiles.
+int shared_prefix_n_chunks(int tiles, int n_kv_heads, int kv_tiles);
+void launch_decode_attn_shared(
+    const uint16_t* qkv, const uint16_t* k_cache, const uint16_t* v_cache,
+    const int32_t* block_table, const int32_t* seq_lens,
+    const int32_t* n_shared, const int32_t* row_tile,
+    const int32_t* row_slot, const int32_t* tile_rows,
+    const int32_t* tile_blocks, const int32_t* tile_bt_row, float* ws_acc,
+    float* ws_ml, uint16_t* out, int batch, int n_tiles, int n_chunks,
+    int n_q_heads, int n_kv_heads, int max_blocks, float scale,
+    int qkv_stride, hipStream_t stream);
+
 // Varlen causal prefill attention over in-batch q/k/v.
 void launch_prefill_attn(
     const uint16_t* q, const uint16_t* k, const uint16_t* v,

@@ -81,6 +81,8 @@ class EngineWorker(Worker):
                  quant=None,
                  spec_lookup: int = 0,
                  device_sampling: bool = False,
+                 shared_prefix_attention: bool = False,
+                 shared_prefix_min_tokens: int = 1024,
                  adapters: Optional[dict] = None,
                  seed: int = 0) -> None:
         super().__init__(device=device_label or f"gpu:{device}",
@@ -122,6 +124,9 @@ class EngineWorker(Worker):
         if kv_dtype not in ("bf16", "fp8"):
             raise ValueError(f"kv_dtype must be bf16 or fp8, got {kv_dtype!r}")
         use_fp8 = kv_dtype == "fp8"
+        if use_fp8 and shared_prefix_attention:
+            raise ValueError("shared_prefix_attention reads a bf16 KV cache "
+                             "only, not kv_dtype fp8")
         kv_torch_dtype = torch.float8_e4m3fn if use_fp8 else torch.bfloat16
         elem_bytes = 1 if use_fp8 else 2
         nb = num_blocks or (default_num_blocks(config, kv_gb,
@@ -145,7 +150,11 @@ class EngineWorker(Worker):
                                 target_step_ms=None if tp_control is not None
                                 else target_step_ms,
                                 spec_lookup=spec_lookup,
-                                device_sampling=device_sampling)
+                                device_sampling=device_sampling,
+                                shared_prefix_attention=
+                                shared_prefix_attention,
+                                shared_prefix_min_tokens=
+                                shared_prefix_min_tokens)
         if use_graphs and torch_device != "cpu":
             from ..engine.graph import install_graph_runner
             install_graph_runner(self.engine)

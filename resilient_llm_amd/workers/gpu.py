@@ -37,6 +37,8 @@ def spawn_gpu_worker(device_index: str, model_name: str,
                      quant: str | None = None,
                      spec_lookup: int | None = None,
                      device_sampling: bool = False,
+                     shared_prefix_attention: bool = False,
+                     shared_prefix_min_tokens: int | None = None,
                      adapters: dict | None = None,
                      extra_env: dict | None = None) -> subprocess.Popen:
     """``device_index`` may be a sub-device replica like ``0.1``: several
@@ -70,6 +72,10 @@ def spawn_gpu_worker(device_index: str, model_name: str,
         cmd += ["--spec-lookup", str(spec_lookup)]
     if device_sampling:
         cmd.append("--device-sampling")
+    if shared_prefix_attention:
+        cmd.append("--shared-prefix-attention")
+        if shared_prefix_min_tokens is not None:
+            cmd += ["--shared-prefix-min-tokens", str(shared_prefix_min_tokens)]
     for name, path in (adapters or {}).items():
         cmd += ["--adapter", f"{name}={path}"]
     return subprocess.Popen(cmd, env=env)
@@ -124,6 +130,10 @@ def register_gpu_workers(config: Config, registry: WorkerRegistry,
         quant = extra.get("quantization")
         spec = extra.get("spec_lookup")
         dev_sampling = bool(extra.get("device_sampling"))
+        shared_kw = {
+            "shared_prefix_attention":
+                bool(extra.get("shared_prefix_attention")),
+            "shared_prefix_min_tokens": extra.get("shared_prefix_min_tokens")}
         # every alias on this worker may declare adapters: the union loads
         adapters = config.worker_adapters("gpu", target)
         eos = extra.get("eos_id")
@@ -135,11 +145,12 @@ def register_gpu_workers(config: Config, registry: WorkerRegistry,
                                 kv_dtype=kv_dtype, quant=quant,
                                 spec_lookup=spec, adapters=adapters,
                                 device_sampling=dev_sampling,
-                                target_step_ms=slo)
+                                target_step_ms=slo, **shared_kw)
         client = RpcWorkerClient(f"gpu:{target}", {model_name}, sock)
         client.proc = proc
         client.respawn = (lambda t=target, m=model_name, s=sock,
-                          adapters=adapters, dev_sampling=dev_sampling:
+                          adapters=adapters, dev_sampling=dev_sampling,
+                          shared_kw=shared_kw:
                           spawn_gpu_worker(t, m, s, kv_gb=kv_gb,
                                            max_batch=max_batch,
                                            use_graphs=use_graphs,
@@ -148,7 +159,7 @@ def register_gpu_workers(config: Config, registry: WorkerRegistry,
                                            spec_lookup=spec,
                                            device_sampling=dev_sampling,
                                            adapters=adapters,
-                                           target_step_ms=slo))
+                                           target_step_ms=slo, **shared_kw))
         registry.register("gpu", target, client)
 
     for pool_name, model_name in sorted(pools.items()):

@@ -33,6 +33,12 @@ def main() -> None:
                     help="serve top_p and presence/frequency penalties "
                          "with the fused device sampler instead of the "
                          "host torch path")
+    ap.add_argument("--shared-prefix-attention", action="store_true",
+                    help="decode rows that share leading KV blocks read "
+                         "them once per group (bf16 KV cache only)")
+    ap.add_argument("--shared-prefix-min-tokens", type=int, default=1024,
+                    help="shortest shared run that forms a group; below "
+                         "1024 a grouped batch gives up the graph replay")
     ap.add_argument("--quant", default=None, choices=(None, "fp8", "int4"),
                     help="fp8: W8A8-fp8 weights for gate_up/down/lm_head "
                          "(rowwise scaled_mm); int4: W4A16 group-128 "
@@ -78,6 +84,10 @@ def main() -> None:
                               quant=args.quant,
                               spec_lookup=args.spec_lookup,
                               device_sampling=args.device_sampling,
+                              shared_prefix_attention=
+                              args.shared_prefix_attention,
+                              shared_prefix_min_tokens=
+                              args.shared_prefix_min_tokens,
                               adapters=dict(a.split("=", 1)
                                             for a in args.adapter or ()),
                               target_step_ms=args.target_step_ms)
