@@ -177,9 +177,13 @@ def _parse_deployment(entry: Any, idx: int) -> Deployment:
                  f"model_list[{idx}].litellm_params.kv_dtype must be "
                  f"bf16|fp8, got {extra['kv_dtype']!r}")
     if "quantization" in extra:
-        _require(extra["quantization"] in ("fp8", "int4"),
+        _require(extra["quantization"] in ("fp8", "int4", "int4-awq"),
                  f"model_list[{idx}].litellm_params.quantization must be "
-                 f"fp8|int4, got {extra['quantization']!r}")
+                 f"fp8|int4|int4-awq, got {extra['quantization']!r}")
+        # AWQ checkpoints do not shard and only gpu/ workers carry the flag
+        _require(extra["quantization"] != "int4-awq" or kind == "gpu",
+                 f"model_list[{idx}].litellm_params.quantization: int4-awq is "
+                 f"served by gpu/<device> workers only, not by {model!r}")
     if "spec_lookup" in extra:
         _require(isinstance(extra["spec_lookup"], int)
                  and 0 <= extra["spec_lookup"] <= 16,
@@ -338,8 +342,8 @@ def load_config(path: str | os.PathLike[str] | None = None,
                      f"deployment {d.model_name}: adapters cannot be "
                      f"combined with quantization: {'|'.join(quants)} on "
                      f"{d.backend_kind}/{d.backend_target} (the fp8 path "
-                     f"hands the MLP fp8 activations, the int4 path has no "
-                     f"bf16 base GEMM to add to)")
+                     f"hands the MLP fp8 activations, the int4 and int4-awq paths "
+                     f"have no bf16 base GEMM to add to)")
             if d.backend_kind == "pool":
                 _require(cluster.pools[d.backend_target].tensor_parallel == 1,
                          f"deployment {d.model_name}: adapters are not "

@@ -143,14 +143,24 @@ class LlamaForCausalLM:
         # the norms stay bf16.  Up to 64 rows run the fused HIP GEMM
         # (ops.w4a16_linear); more rows dequantize one projection at a
         # time into a shared scratch buffer and take the bf16 GEMM.
-        if quant not in (None, "fp8", "int4"):
-            raise ValueError(f"quant must be None, 'fp8' or 'int4', "
-                             f"got {quant!r}")
-        if (quant == "int4" and torch.device(device).type == "cuda"
+        # quant="int4-awq": the int4 path with a per-group zero-point and fp16
+        # scales (ops.w4a16_zp_linear / ops.w4_zp_dequant), the form
+        # AutoAWQ checkpoints hold: load_safetensors repacks their
+        # tensors on the device (ops.awq_repack); random init quantizes
+        # asymmetric min/max round-to-nearest.  (A mode of the int4 path,
+        # hence the name; a bare "awq" stays an unknown value.)
+        if quant not in (None, "fp8", "int4", "int4-awq"):
+            raise ValueError(f"quant must be None, 'fp8', 'int4' or "
+                             f"'int4-awq', got {quant!r}")
+        if (quant in ("int4", "int4-awq")
+                and torch.device(device).type == "cuda"
                 and dtype != torch.bfloat16):
-            raise ValueError(f"quant='int4' on a GPU needs dtype bfloat16 "
+            raise ValueError(f"quant={quant!r} on a GPU needs dtype bfloat16 "
                              f"(the fused kernel reads bf16 activations), "
                              f"got {dtype}")
+        if quant == "int4-awq" and tp_world > 1:
+            raise ValueError("quant='int4-awq' does not shard: "
+                             "tensor_parallel must be 1")
         self.quant = quant
         self.tp_rank = tp_rank
         self.tp_world = tp_world
@@ -181,6 +191,8 @@ class LlamaForCausalLM:
             self._quantize_weights()
         elif self.quant == "int4":
             self._quantize_weights_int4()
+        elif self.quant == "int4-awq":
+            self._quantize_weights_awq()
         self.cos_sin = ops.build_cos_sin(c.max_position, c.head_dim,
                                          c.rope_theta, device=self.device)
 
@@ -294,6 +306,23 @@ class LlamaForCausalLM:
                 self.params[name + ".q4"] = _ref.w4_pack(q)
                 self.params[name + ".s4"] = s
                 del self.params[name]
+        self._w4_alloc_shared()
+
+    def _quantize_weights_awq(self) -> None:
+        """Random-initialised weights under quant="int4-awq": asymmetric
+        group-128 round-to-nearest into the packed / meta pair a loaded
+        AWQ checkpoint gives, bf16 originals freed."""
+        from ..ops import ref as _ref
+        for i in range(self.config.n_layers):
+            for n in self._w4_shapes():
+                name = f"l{i}.{n}"
+                u, z, s = _ref.quantize_w4_zp(self.params.pop(name))
+                self.params[name + ".q4"] = _ref.w4_pack(u.to(torch.int8) - 8)
+                self.params[name + ".m4"] = _ref.w4_zp_meta(z, s)
+        self._w4_alloc_shared()
+
+    def _w4_alloc_shared(self) -> None:
+        shapes = self._w4_shapes()
         if self.device.type == "cuda" and self._w4_scratch is None:
             # one dequant buffer for the largest projection and one
             # split-K slab for the widest launch, shared by all layers
@@ -309,6 +338,16 @@ class LlamaForCausalLM:
 
     def _linear_w4(self, x: torch.Tensor, name: str) -> torch.Tensor:
         q4 = self.params[name + ".q4"]
+        if self.quant == "int4-awq":
+            m4 = self.params[name + ".m4"]
+            if not x.is_cuda:
+                return ops.w4a16_zp_linear(x, q4, m4)  # the reference
+            if x.shape[0] <= self._W4_FUSED_ROWS:
+                return ops.w4a16_zp_linear(x, q4, m4, ws=self._w4_slab)
+            N, K = m4.shape[0], x.shape[1]
+            w = ops.w4_zp_dequant(
+                q4, m4, out=self._w4_scratch[:N * K].view(N, K))
+            return _linear(x, w)
         s4 = self.params[name + ".s4"]
         if not x.is_cuda:
             return ops.w4a16_linear(x, q4, s4)     # the reference
@@ -336,6 +375,16 @@ class LlamaForCausalLM:
         raw: dict[str, torch.Tensor] = {}
         for f in files:
             raw.update(st.load_file(os.path.join(path, f)))
+        is_awq = any(k.endswith(".qweight") for k in raw)
+        if is_awq != (self.quant == "int4-awq"):
+            raise ValueError(
+                f"{path} holds {'AWQ int4' if is_awq else 'dense'} weights "
+                f"but the model was built with quant={self.quant!r}: "
+                + ("AWQ checkpoints load under quant='int4-awq' only"
+                   if is_awq else "quant='int4-awq' loads AWQ checkpoints "
+                   "only (nothing is quantized at load)"))
+        if is_awq:
+            return self._load_awq(raw, path)
 
         def take(name, rows: Optional[int] = None, cols: Optional[int] = None):
             """Move to device taking only this rank's shard: ``rows`` =
@@ -375,6 +424,87 @@ class LlamaForCausalLM:
             self._quantize_weights()
         elif self.quant == "int4":
             self._quantize_weights_int4()
+        return loaded
+
+    _AWQ_CONFIG = {"quant_method": "awq", "bits": 4, "group_size": 128,
+                   "version": "gemm", "zero_point": True}
+
+    @classmethod
+    def _check_awq_config(cls, path: str) -> None:
+        """``config.json``'s quantization_config, when there is one, must
+        describe the one layout the repack kernel reads."""
+        import json
+        cfg_path = os.path.join(path, "config.json")
+        if not os.path.exists(cfg_path):
+            return
+        with open(cfg_path) as f:
+            qc = json.load(f).get("quantization_config")
+        if qc is None:
+            return
+        for field, want in cls._AWQ_CONFIG.items():
+            got = qc.get(field)
+            if isinstance(want, str) and isinstance(got, str):
+                got = got.lower()
+            if got != want or type(got) is not type(want):
+                raise ValueError(
+                    f"{cfg_path}: quantization_config.{field} must be "
+                    f"{want!r}, got {qc.get(field)!r}")
+
+    def _load_awq(self, raw: dict, path: str) -> int:
+        """An AutoAWQ Llama checkpoint (GEMM layout, 4 bits, group 128):
+        every projection's qweight / qzeros / scales go to the device as
+        they are and ``ops.awq_repack`` writes them into the fused
+        packed / meta pair - q/k/v and gate/up at their column offsets.
+        embed, norms and lm_head are cast to the model dtype."""
+        from ..ops import ref as _ref
+        self._check_awq_config(path)
+        c = self.config
+        loaded = 0
+
+        def dense(name):
+            nonlocal loaded
+            loaded += 1
+            return raw[name].to(self.dtype).to(self.device).contiguous()
+
+        def fused(i, n, parts):
+            nonlocal loaded
+            N, K = self._w4_shapes()[n]
+            packed = torch.empty(N * K // 8, dtype=torch.int32,
+                                 device=self.device)
+            meta = torch.empty((N, K // _ref.W4_GROUP), dtype=torch.int32,
+                               device=self.device)
+            col = 0
+            for part in parts:
+                base = f"model.layers.{i}.{part}."
+                qw, qz, sc = (raw[base + t].to(self.device).contiguous()
+                              for t in ("qweight", "qzeros", "scales"))
+                if qw.shape[0] != K:
+                    raise ValueError(f"{base}qweight has K={qw.shape[0]}, "
+                                     f"the model {K}")
+                ops.awq_repack(qw, qz, sc, packed, meta, col)
+                col += sc.shape[1]
+                loaded += 3
+            if col != N:
+                raise ValueError(f"layer {i} {n}: checkpoint has {col} "
+                                 f"output columns, the model {N}")
+            self.params.pop(f"l{i}.{n}", None)
+            self.params[f"l{i}.{n}.q4"] = packed
+            self.params[f"l{i}.{n}.m4"] = meta
+
+        self.params["embed"] = dense("model.embed_tokens.weight")
+        for i in range(c.n_layers):
+            fused(i, "qkv", [f"self_attn.{x}_proj" for x in "qkv"])
+            fused(i, "o", ["self_attn.o_proj"])
+            fused(i, "gate_up", ["mlp.gate_proj", "mlp.up_proj"])
+            fused(i, "down", ["mlp.down_proj"])
+            p = f"model.layers.{i}."
+            self.params[f"l{i}.ln1"] = dense(p + "input_layernorm.weight")
+            self.params[f"l{i}.ln2"] = dense(
+                p + "post_attention_layernorm.weight")
+        self.params["final_ln"] = dense("model.norm.weight")
+        self.params["lm_head"] = dense("lm_head.weight") \
+            if "lm_head.weight" in raw else self.params["embed"]
+        self._w4_alloc_shared()
         return loaded
 
     def save_safetensors(self, path: str) -> None:
@@ -591,7 +721,7 @@ class LlamaForCausalLM:
             h = ops.rmsnorm(x, p[f"l{i}.ln1"], c.rms_eps)
         else:
             h = ops.rmsnorm_residual_(x, residual, p[f"l{i}.ln1"], c.rms_eps)
-        if self.quant == "int4":
+        if self.quant in ("int4", "int4-awq"):
             return self._layer_w4(i, h, residual, kv_cache, attn_fn)
         qkv = _linear(h, p[f"l{i}.qkv"])
         k_cache, v_cache = kv_cache.layer(i)

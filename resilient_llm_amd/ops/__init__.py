@@ -472,4 +472,60 @@ def w4_dequant(packed: torch.Tensor, s: torch.Tensor,
     return ref.w4_dequant(packed, s, out)
 
 
+def w4a16_zp_linear(x: torch.Tensor, packed: torch.Tensor,
+                    meta: torch.Tensor, splitk: int = 0,
+                    out: torch.Tensor | None = None,
+                    ws: torch.Tensor | None = None) -> torch.Tensor:
+    """``w4a16_linear`` for zero-point (AWQ) weights: out[m, n] =
+    bf16(sum_g s[n, g] * sum_{k in g} x[m, k] * (u[n, k] - z[n, g])),
+    ``packed`` the nibbles u in ``ref.w4_pack`` order, ``meta`` int32
+    [N, K/128] from ``ref.w4_zp_meta`` (or both from ``awq_repack``).
+    Shapes, slicing, ``out`` / ``ws`` and the row contract are those of
+    ``w4a16_linear``."""
+    if x.is_cuda:
+        _gpu()
+        if out is None:
+            out = torch.empty((x.shape[0], meta.shape[0]), dtype=x.dtype,
+                              device=x.device)
+        torch.ops.rlli.w4a16_zp_linear_(x, packed, meta, splitk, out, ws)
+        return out
+    y = ref.w4a16_zp_linear(x, packed, meta)
+    if out is None:
+        return y
+    out.copy_(y)
+    return out
+
+
+def w4_zp_dequant(packed: torch.Tensor, meta: torch.Tensor,
+                  out: torch.Tensor | None = None) -> torch.Tensor:
+    """bf16 [N, K] = bf16(f32(s) * (u - z)) of a zero-point int4 weight,
+    into ``out`` when given."""
+    if packed.is_cuda:
+        _gpu()
+        if out is None:
+            out = torch.empty((meta.shape[0], meta.shape[1] * ref.W4_GROUP),
+                              dtype=torch.bfloat16, device=packed.device)
+        torch.ops.rlli.w4_zp_dequant_(packed, meta, out)
+        return out
+    return ref.w4_zp_dequant(packed, meta, out)
+
+
+def awq_repack(qweight: torch.Tensor, qzeros: torch.Tensor,
+               scales: torch.Tensor, packed: torch.Tensor,
+               meta: torch.Tensor, col_offset: int = 0) -> None:
+    """One projection of an AutoAWQ checkpoint (GEMM layout, 4 bits, group
+    128: ``qweight`` int32 [K, N/8], ``qzeros`` int32 [K/128, N/8],
+    ``scales`` fp16 [K/128, N]) into output columns ``col_offset`` ..
+    ``col_offset + N`` of ``packed`` int32 [N_total*K/8] and ``meta`` int32
+    [N_total, K/128]: q/k/v and gate/up repack straight into their slice
+    of the fused tensors.  N and col_offset are multiples of 64; nothing
+    outside the slice is written."""
+    if qweight.is_cuda:
+        _gpu()
+        torch.ops.rlli.awq_repack_(qweight, qzeros, scales, packed, meta,
+                                   col_offset)
+        return
+    ref.awq_repack(qweight, qzeros, scales, packed, meta, col_offset)
+
+
 build_cos_sin = ref.build_cos_sin

@@ -652,11 +652,18 @@ Tensor skinny2_silu_linear(const Tensor& gu, const Tensor& w, int64_t splitk) {
 
 // --------------------------------------------------------------- w4a16
 // int4 group-quantized weights: packed int32 [N*K/8] in the fragment
-// order of ops/ref.py w4_pack, s bf16 [N, K/128].
-void check_w4(const Tensor& packed, const Tensor& s, const Tensor& like) {
+// order of ops/ref.py w4_pack, s bf16 [N, K/128] - or, for the zero-point
+// forms (``zp``), meta int32 [N, K/128] (ops/ref.py w4_zp_meta).
+void check_w4(const Tensor& packed, const Tensor& s, const Tensor& like,
+              bool zp = false) {
   TORCH_CHECK(s.dim() == 2 && s.size(0) >= 1 && s.size(1) >= 1,
-              "s must be [N, K/128]");
-  check_bf16_contig(s, "s");
+              zp ? "meta" : "s", " must be [N, K/128]");
+  if (zp) {
+    TORCH_CHECK(s.scalar_type() == at::kInt && s.is_contiguous() &&
+                s.is_cuda(), "meta must be contiguous int32 on the GPU");
+  } else {
+    check_bf16_contig(s, "s");
+  }
   const int64_t N = s.size(0), K = s.size(1) * 128;
   TORCH_CHECK(N % 64 == 0, "int4 weights need N % 64 == 0, got N=", N);
   TORCH_CHECK(N * K / 2 < (int64_t(1) << 31), "int4 weight too large");
@@ -684,13 +691,13 @@ std::vector<int64_t> w4a16_plan(int64_t N, int64_t K, int64_t splitk) {
 // first slices*M*N floats of the split-K slab: ``ws`` when the caller
 // owns one (>= that many f32), else a caching-allocator tensor, which
 // inside hipGraph capture comes from the graph's pool.
-void w4a16_linear_(const Tensor& x, const Tensor& packed, const Tensor& s,
-                   int64_t splitk, Tensor out,
-                   const c10::optional<Tensor>& ws_opt) {
+void w4a16_linear_any(const Tensor& x, const Tensor& packed, const Tensor& s,
+                      int64_t splitk, Tensor out,
+                      const c10::optional<Tensor>& ws_opt, bool zp) {
   check_bf16_contig(x, "x");
   check_bf16_contig(out, "out");
   TORCH_CHECK(x.dim() == 2, "x must be [M, K]");
-  check_w4(packed, s, x);
+  check_w4(packed, s, x, zp);
   const int M = int(x.size(0));
   const int K = int(x.size(1));
   const int N = int(s.size(0));
@@ -722,11 +729,29 @@ void w4a16_linear_(const Tensor& x, const Tensor& packed, const Tensor& s,
     ws_ptr = ws.data_ptr<float>();
   }
   c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
-  rlli::launch_w4a16(bf16_ptr(x),
-                     reinterpret_cast<const uint32_t*>(packed.data_ptr()),
-                     bf16_ptr(s), ws_ptr, bf16_ptr(out), M, N, K, sk, gps,
-                     current_stream(x));
-  check_launch("w4a16_linear");
+  const auto* pk = reinterpret_cast<const uint32_t*>(packed.data_ptr());
+  if (zp) {
+    rlli::launch_w4a16_zp(bf16_ptr(x), pk,
+                          reinterpret_cast<const uint32_t*>(s.data_ptr()),
+                          ws_ptr, bf16_ptr(out), M, N, K, sk, gps,
+                          current_stream(x));
+  } else {
+    rlli::launch_w4a16(bf16_ptr(x), pk, bf16_ptr(s), ws_ptr, bf16_ptr(out),
+                       M, N, K, sk, gps, current_stream(x));
+  }
+  check_launch(zp ? "w4a16_zp_linear" : "w4a16_linear");
+}
+
+void w4a16_linear_(const Tensor& x, const Tensor& packed, const Tensor& s,
+                   int64_t splitk, Tensor out,
+                   const c10::optional<Tensor>& ws_opt) {
+  w4a16_linear_any(x, packed, s, splitk, out, ws_opt, false);
+}
+
+void w4a16_zp_linear_(const Tensor& x, const Tensor& packed,
+                      const Tensor& meta, int64_t splitk, Tensor out,
+                      const c10::optional<Tensor>& ws_opt) {
+  w4a16_linear_any(x, packed, meta, splitk, out, ws_opt, true);
 }
 
 void w4_dequant_(const Tensor& packed, const Tensor& s, Tensor out) {
@@ -740,6 +765,62 @@ void w4_dequant_(const Tensor& packed, const Tensor& s, Tensor out) {
       reinterpret_cast<const uint32_t*>(packed.data_ptr()), bf16_ptr(s),
       bf16_ptr(out), int(N), int(K), current_stream(out));
   check_launch("w4_dequant_");
+}
+
+void w4_zp_dequant_(const Tensor& packed, const Tensor& meta, Tensor out) {
+  check_bf16_contig(out, "out");
+  check_w4(packed, meta, out, true);
+  const int64_t N = meta.size(0), K = meta.size(1) * 128;
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == N && out.size(1) == K,
+              "out must be [N, K] = [", N, ", ", K, "]");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(out.device());
+  rlli::launch_w4_zp_dequant(
+      reinterpret_cast<const uint32_t*>(packed.data_ptr()),
+      reinterpret_cast<const uint32_t*>(meta.data_ptr()), bf16_ptr(out),
+      int(N), int(K), current_stream(out));
+  check_launch("w4_zp_dequant_");
+}
+
+// AutoAWQ GEMM tensors of one projection -> columns col_offset ..
+// col_offset + N of the fused packed / meta [N_total, K/128].
+void awq_repack_(const Tensor& qweight, const Tensor& qzeros,
+                 const Tensor& scales, Tensor packed, Tensor meta,
+                 int64_t col_offset) {
+  TORCH_CHECK(qweight.dim() == 2 && qzeros.dim() == 2 && scales.dim() == 2,
+              "qweight, qzeros and scales must be 2-d");
+  const int64_t K = qweight.size(0), N = scales.size(1), G = K / 128;
+  TORCH_CHECK(K >= 128 && K % 128 == 0 && N >= 64 && N % 64 == 0,
+              "awq_repack needs K % 128 == 0 and N % 64 == 0, got K=", K,
+              " N=", N);
+  for (const Tensor* t : {&qweight, &qzeros}) {
+    TORCH_CHECK(t->scalar_type() == at::kInt && t->is_contiguous() &&
+                t->is_cuda(),
+                "qweight / qzeros must be contiguous int32 on the GPU");
+  }
+  TORCH_CHECK(scales.scalar_type() == at::kHalf && scales.is_contiguous() &&
+              scales.is_cuda(), "scales must be contiguous fp16 on the GPU");
+  TORCH_CHECK(qweight.size(1) == N / 8 && qzeros.size(0) == G &&
+              qzeros.size(1) == N / 8 && scales.size(0) == G,
+              "AWQ GEMM layout needs qweight [K, N/8], qzeros [K/128, N/8], "
+              "scales [K/128, N]");
+  check_w4(packed, meta, qweight, true);
+  const int64_t n_total = meta.size(0);
+  TORCH_CHECK(meta.size(1) == G, "meta has ", meta.size(1), " groups, the "
+              "checkpoint tensors ", G);
+  TORCH_CHECK(col_offset >= 0 && col_offset % 64 == 0 &&
+              col_offset + N <= n_total, "col_offset ", col_offset, " + N ",
+              N, " must be a multiple of 64 inside N_total = ", n_total);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qweight.data_ptr()) % 16 == 0,
+              "qweight must be 16-byte aligned");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(qweight.device());
+  rlli::launch_awq_repack(
+      reinterpret_cast<const uint32_t*>(qweight.data_ptr()),
+      reinterpret_cast<const uint32_t*>(qzeros.data_ptr()),
+      reinterpret_cast<const uint16_t*>(scales.data_ptr()),
+      reinterpret_cast<uint32_t*>(packed.data_ptr()),
+      reinterpret_cast<uint32_t*>(meta.data_ptr()), int(N), int(K),
+      int(col_offset), current_stream(qweight));
+  check_launch("awq_repack_");
 }
 
 Tensor stream_probe(const Tensor& w, int64_t splitk) {
@@ -1147,6 +1228,11 @@ TORCH_LIBRARY(rlli, m) {
         "Tensor(a!) out, Tensor(b!)? ws) -> ()");
   m.def("w4a16_plan(int N, int K, int splitk) -> int[]", &w4a16_plan);
   m.def("w4_dequant_(Tensor packed, Tensor s, Tensor(a!) out) -> ()");
+  m.def("w4a16_zp_linear_(Tensor x, Tensor packed, Tensor meta, int splitk, "
+        "Tensor(a!) out, Tensor(b!)? ws) -> ()");
+  m.def("w4_zp_dequant_(Tensor packed, Tensor meta, Tensor(a!) out) -> ()");
+  m.def("awq_repack_(Tensor qweight, Tensor qzeros, Tensor scales, "
+        "Tensor(a!) packed, Tensor(b!) meta, int col_offset) -> ()");
   m.def("stream_probe(Tensor w, int splitk) -> Tensor");
   m.def("prefill_paged_attn(Tensor qkv, Tensor k_cache, Tensor v_cache, "
         "Tensor chunk_row0, Tensor chunk_pos0, Tensor chunk_nrows, "
@@ -1183,6 +1269,9 @@ TORCH_LIBRARY_IMPL(rlli, CUDA, m) {
   m.impl("skinny2_silu_linear", &skinny2_silu_linear);
   m.impl("w4a16_linear_", &w4a16_linear_);
   m.impl("w4_dequant_", &w4_dequant_);
+  m.impl("w4a16_zp_linear_", &w4a16_zp_linear_);
+  m.impl("w4_zp_dequant_", &w4_zp_dequant_);
+  m.impl("awq_repack_", &awq_repack_);
   m.impl("stream_probe", &stream_probe);
   m.impl("prefill_paged_attn", &prefill_paged_attn);
   m.impl("kv_copy_blocks_", &kv_copy_blocks_);

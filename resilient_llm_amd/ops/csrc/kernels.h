@@ -163,6 +163,22 @@ void launch_w4a16(const uint16_t* x, const uint32_t* packed,
                   int K, int splitk, int grp_per_slice, hipStream_t stream);
 void launch_w4_dequant(const uint32_t* packed, const uint16_t* s,
                        uint16_t* out, int N, int K, hipStream_t stream);
+// Zero-point forms (w4a16_zp.hip): w = f32(s) * (u - z) with u the packed
+// nibble and meta[N, K/128] = fp16 s | bf16(-(128 + z)) << 16.  Same
+// contract and slicing as above.
+//   launch_awq_repack: AutoAWQ GEMM tensors (qweight [K, N/8], qzeros
+//     [K/128, N/8], scales fp16 [K/128, N]) -> columns col_offset ..
+//     col_offset + N of packed / meta; N % 64 == 0, col_offset % 64 == 0.
+void launch_w4a16_zp(const uint16_t* x, const uint32_t* packed,
+                     const uint32_t* meta, float* ws, uint16_t* out, int M,
+                     int N, int K, int splitk, int grp_per_slice,
+                     hipStream_t stream);
+void launch_w4_zp_dequant(const uint32_t* packed, const uint32_t* meta,
+                          uint16_t* out, int N, int K, hipStream_t stream);
+void launch_awq_repack(const uint32_t* qweight, const uint32_t* qzeros,
+                       const uint16_t* scales, uint32_t* packed,
+                       uint32_t* meta, int N, int K, int col_offset,
+                       hipStream_t stream);
 
 void launch_skinny_gemm(const uint16_t* x, const uint16_t* w, float* ws,
                         uint16_t* out, int M, int N, int K, int splitk,

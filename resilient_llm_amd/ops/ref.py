@@ -527,3 +527,125 @@ def w4_dequant(packed: torch.Tensor, s: torch.Tensor,
         return w
     out.copy_(w)
     return out
+
+
+# ---- AWQ int4 checkpoints (zero-point W4A16) ----
+# AutoAWQ "GEMM" layout, 4 bits, group 128: ``qweight`` int32 [K, N/8],
+# ``qzeros`` int32 [K/128, N/8], ``scales`` fp16 [K/128, N].  A dword of
+# either int32 tensor packs 8 consecutive output columns: nibble i (bits
+# 4i..4i+3) holds column 8*c + AWQ_ORDER[i]; columns 0..7 = 0..7 pack to
+# 0x75316420.  w[n, k] = f32(scales[k/128, n]) * (u[k, n] - z[k/128, n]),
+# u and z in 0..15.  On the device the nibbles u sit in the ``w4_pack``
+# fragment order (``w4_pack(u - 8)``: the nibble stored there is q + 8)
+# and scale and zero-point travel as one int32 ``meta[N, G]``: the fp16
+# scale bits in the low half, the bf16 bits of -(128 + z) = 0xC300 | z in
+# the high half.  Scales stay fp16 bit for bit.
+AWQ_ORDER = (0, 2, 4, 6, 1, 3, 5, 7)
+_AWQ_NIBBLE_OF_COL = (0, 4, 1, 5, 2, 6, 3, 7)
+
+
+def _awq_nibbles(t: torch.Tensor) -> torch.Tensor:
+    """int32 [R, C] -> uint8 [R, 8*C], column order restored."""
+    sh = torch.tensor([4 * i for i in _AWQ_NIBBLE_OF_COL], dtype=torch.int64,
+                      device=t.device)
+    v = (t.to(torch.int64).unsqueeze(-1) >> sh) & 15
+    return v.reshape(t.shape[0], -1).to(torch.uint8)
+
+
+def awq_unpack(qweight: torch.Tensor, qzeros: torch.Tensor,
+               scales: torch.Tensor):
+    """AWQ tensors -> (u uint8 [N, K], z uint8 [N, G], s fp16 [N, G])."""
+    K, N = qweight.shape[0], scales.shape[1]
+    _w4_check_shape(N, K)
+    G = K // W4_GROUP
+    if (qweight.dtype != torch.int32 or qzeros.dtype != torch.int32
+            or scales.dtype != torch.float16
+            or tuple(qweight.shape) != (K, N // 8)
+            or tuple(qzeros.shape) != (G, N // 8)
+            or tuple(scales.shape) != (G, N)):
+        raise ValueError(
+            f"AWQ GEMM layout needs qweight int32 [K, N/8], qzeros int32 "
+            f"[K/128, N/8], scales fp16 [K/128, N]; got "
+            f"{qweight.dtype} {tuple(qweight.shape)}, {qzeros.dtype} "
+            f"{tuple(qzeros.shape)}, {scales.dtype} {tuple(scales.shape)}")
+    return (_awq_nibbles(qweight).t().contiguous(),
+            _awq_nibbles(qzeros).t().contiguous(),
+            scales.t().contiguous())
+
+
+def quantize_w4_zp(w: torch.Tensor):
+    """W [N, K] -> (u uint8 [N, K], z uint8 [N, G], s fp16 [N, G]):
+    asymmetric min/max round-to-nearest per group of 128.  The range is
+    widened to hold 0 so that z fits 0..15, and s is rounded up to fp16
+    so that 15 s covers it: |W - s (u - z)| <= s / 2 for every weight."""
+    N, K = w.shape
+    _w4_check_shape(N, K)
+    f = w.double().reshape(N, K // W4_GROUP, W4_GROUP)
+    lo = f.amin(dim=-1).clamp_max(0.0)
+    hi = f.amax(dim=-1).clamp_min(0.0)
+    tiny = torch.finfo(torch.float16).tiny
+    s = ((hi - lo) / 15.0).clamp_min(tiny).to(torch.float16)
+    short = s.double() * 15.0 < hi - lo
+    s = torch.where(short, (s.view(torch.int16) + 1).view(torch.float16), s)
+    sd = s.double()
+    z = torch.round(-lo / sd).clamp_(0, 15)
+    u = (torch.round(f / sd.unsqueeze(-1)) + z.unsqueeze(-1)).clamp_(0, 15)
+    return (u.reshape(N, K).to(torch.uint8), z.to(torch.uint8),
+            s.contiguous())
+
+
+def w4_zp_meta(z: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+    """(z uint8 [N, G], s fp16 [N, G]) -> int32 [N, G] the kernels read."""
+    if s.dtype != torch.float16 or z.shape != s.shape:
+        raise ValueError("w4_zp_meta: z and fp16 s must both be [N, G]")
+    if int(z.max()) > 15:
+        raise ValueError("w4_zp_meta: z must be in 0..15")
+    lo = s.contiguous().view(torch.int16).to(torch.int64) & 0xFFFF
+    d = ((0xC300 | z.to(torch.int64)) << 16) | lo
+    return (d - 2 ** 32).to(torch.int32).contiguous()
+
+
+def _w4_zp_parts(packed: torch.Tensor, meta: torch.Tensor):
+    """(u - z float32 [N, G, 128], s float32 [N, G]) of a packed weight."""
+    N, G = meta.shape
+    u = w4_unpack(packed, N, G * W4_GROUP).float() + 8.0
+    m = meta.to(torch.int64)
+    z = ((m >> 16) & 15).float()
+    s = (m & 0xFFFF).to(torch.uint16).view(torch.float16).float()
+    return u.reshape(N, G, W4_GROUP) - z.unsqueeze(-1), s
+
+
+def w4a16_zp_linear(x: torch.Tensor, packed: torch.Tensor,
+                    meta: torch.Tensor) -> torch.Tensor:
+    """``w4a16_linear`` with a zero-point: out[m, n] = round(sum_g
+    f32(s[n, g]) * sum_{k in g} f32(x[m, k]) * (u[n, k] - z[n, g]))."""
+    d, s = _w4_zp_parts(packed, meta)
+    N, G = meta.shape
+    xf = x.float().reshape(x.shape[0], G, W4_GROUP)
+    part = torch.einsum("mgk,ngk->mng", xf, d)
+    return (part * s.unsqueeze(0)).sum(dim=-1).to(x.dtype)
+
+
+def w4_zp_dequant(packed: torch.Tensor, meta: torch.Tensor,
+                  out: torch.Tensor | None = None) -> torch.Tensor:
+    """bf16 [N, K] = bf16(f32(s) * (u - z)): one rounding per weight."""
+    d, s = _w4_zp_parts(packed, meta)
+    w = (d * s.unsqueeze(-1)).reshape(meta.shape[0], -1).to(torch.bfloat16)
+    if out is None:
+        return w
+    out.copy_(w)
+    return out
+
+
+def awq_repack(qweight, qzeros, scales, packed, meta, col_offset):
+    """CPU path of ``ops.awq_repack``: write columns col_offset ..
+    col_offset + N of the fused ``packed`` / ``meta`` [N_total, G]."""
+    u, z, s = awq_unpack(qweight, qzeros, scales)
+    N, K = u.shape
+    G = K // W4_GROUP
+    if col_offset % 64 or col_offset < 0 or col_offset + N > meta.shape[0] \
+            or meta.shape[1] != G or packed.numel() != meta.shape[0] * K // 8:
+        raise ValueError("awq_repack: slice does not fit packed / meta")
+    lo = col_offset // 16 * G * 256
+    packed[lo:lo + N * K // 8] = w4_pack(u.to(torch.int8) - 8)
+    meta[col_offset:col_offset + N] = w4_zp_meta(z, s)

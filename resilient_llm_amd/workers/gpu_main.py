@@ -39,10 +39,13 @@ def main() -> None:
     ap.add_argument("--shared-prefix-min-tokens", type=int, default=1024,
                     help="shortest shared run that forms a group; below "
                          "1024 a grouped batch gives up the graph replay")
-    ap.add_argument("--quant", default=None, choices=(None, "fp8", "int4"),
+    ap.add_argument("--quant", default=None,
+                    choices=(None, "fp8", "int4", "int4-awq"),
                     help="fp8: W8A8-fp8 weights for gate_up/down/lm_head "
                          "(rowwise scaled_mm); int4: W4A16 group-128 "
-                         "weights for qkv/o/gate_up/down (fused HIP GEMM)")
+                         "weights for qkv/o/gate_up/down (fused HIP GEMM); "
+                         "int4-awq: the same with zero-points, for --weights "
+                         "that hold an AutoAWQ int4 checkpoint")
     ap.add_argument("--kv-dtype", default="bf16", choices=("bf16", "fp8"),
                     help="paged-KV-cache element type: fp8-e4m3 halves "
                          "bytes/token (2x KV capacity per GiB)")

@@ -16,7 +16,16 @@ End to end (--e2e).  The engine as the serving worker builds it (decode
 graphs, batch 64), 64 requests of 128 prompt and 64 output tokens,
 bf16 and int4 alternated A B A B.  Prints reqs/s and param_bytes().
 
-Usage: python scripts/bench_w4a16.py [--iters N] [--e2e] [--model NAME]
+Zero-point (--zp).  The same kernel-level method for the AWQ form:
+  (z) ops.w4a16_zp_linear on packed + meta;
+  (a) ops.w4a16_linear, the symmetric kernel, on the same packed buffers;
+  (b) ops.w4_zp_dequant into one scratch buffer + the model's bf16 GEMM.
+Then ops.awq_repack of one Llama-3-8B layer's seven projections (q, k, v,
+o, gate, up, down) from AutoAWQ tensors into the four fused pairs, timed
+as one unit, rotating over enough layers to miss the cache.
+
+Usage: python scripts/bench_w4a16.py [--iters N] [--zp] [--e2e]
+                                     [--model NAME]
 """
 import argparse
 import json
@@ -109,6 +118,105 @@ def kernel_level(iters, splitk):
     print(json.dumps({"w4a16_kernel_level": rows}))
 
 
+def kernel_level_zp(iters, splitk):
+    from resilient_llm_amd.ops import ref
+    print(f"{'N':>6} {'K':>6} {'M':>3} {'(z) zp fused us':>16} "
+          f"{'(a) sym fused us':>17} {'(b) zp deq+gemm us':>19} {'z/a':>6} "
+          f"{'b/z':>6} {'(z) packed GB/s':>16}")
+    rows = []
+    for N, K in SHAPES:
+        G = K // 128
+        packed_bytes = N * K // 2 + N * G * 4
+        nq = n_buffers(packed_bytes)
+        g = torch.Generator(device=DEV).manual_seed(N + K)
+        packed = [torch.randint(-2 ** 31, 2 ** 31 - 1, (N * K // 8,),
+                                dtype=torch.int32, device=DEV, generator=g)
+                  for _ in range(nq)]
+        scales = [0.003 * (1 + torch.rand(N, G, device=DEV, generator=g))
+                  for _ in range(nq)]
+        meta = [ref.w4_zp_meta(
+            torch.randint(0, 16, (N, G), dtype=torch.uint8, device=DEV,
+                          generator=g), s.half()) for s in scales]
+        scales = [s.bfloat16() for s in scales]
+        scratch = torch.empty(N, K, dtype=torch.bfloat16, device=DEV)
+        slab = torch.empty(ops.w4a16_plan(N, K, splitk)[0] * 64 * N,
+                           dtype=torch.float32, device=DEV)
+        for M in ROWS:
+            x = torch.randn(M, K, device=DEV, generator=g).bfloat16()
+
+            def zp(i):
+                return ops.w4a16_zp_linear(x, packed[i % nq], meta[i % nq],
+                                           splitk, ws=slab)
+
+            def sym(i):
+                return ops.w4a16_linear(x, packed[i % nq], scales[i % nq],
+                                        splitk, ws=slab)
+
+            def deq_gemm(i):
+                w = ops.w4_zp_dequant(packed[i % nq], meta[i % nq],
+                                      out=scratch)
+                return llama._linear(x, w)
+
+            for i in range(10):
+                zp(i), sym(i), deq_gemm(i)
+            tz, ta, tb = [], [], []
+            for i in range(iters):
+                tz.append(timed(lambda: zp(i)))
+                ta.append(timed(lambda: sym(i)))
+                tb.append(timed(lambda: deq_gemm(i)))
+            torch.cuda.synchronize()
+            z, a, b = med(tz), med(ta), med(tb)
+            rows.append(dict(N=N, K=K, M=M, zp_fused_us=z, sym_fused_us=a,
+                             zp_deq_gemm_us=b))
+            print(f"{N:6d} {K:6d} {M:3d} {z:16.2f} {a:17.2f} {b:19.2f} "
+                  f"{z / a:6.2f} {b / z:6.2f} {packed_bytes / z / 1e3:16.1f}",
+                  flush=True)
+        del packed, scales, meta, scratch, slab
+        torch.cuda.empty_cache()
+    lost = [r for r in rows if r["zp_fused_us"] >= r["zp_deq_gemm_us"]]
+    print("gate (z) < (b) at every point:", "HOLDS" if not lost else
+          f"FAILS at {[(r['N'], r['K'], r['M']) for r in lost]}")
+    print(json.dumps({"w4a16_zp_kernel_level": rows}))
+    repack_layer(max(10, iters // 4))
+
+
+def repack_layer(iters):
+    """One 8B layer: (fused N, K, part widths) as the loader repacks it."""
+    layer = [(6144, 4096, (4096, 1024, 1024)), (4096, 4096, (4096,)),
+             (28672, 4096, (14336, 14336)), (4096, 14336, (4096,))]
+    src_bytes = sum(N * K // 2 + (K // 128) * (N // 2 + 2 * N)
+                    for N, K, _ in layer)
+    nl = n_buffers(src_bytes)
+    g = torch.Generator(device=DEV).manual_seed(7)
+
+    def i32(*shape):
+        return torch.randint(-2 ** 31, 2 ** 31 - 1, shape, dtype=torch.int32,
+                             device=DEV, generator=g)
+    src = [[[(i32(K, w // 8), i32(K // 128, w // 8),
+              torch.rand(K // 128, w, device=DEV, generator=g).half())
+             for w in widths] for _, K, widths in layer] for _ in range(nl)]
+    dst = [(torch.empty(N * K // 8, dtype=torch.int32, device=DEV),
+            torch.empty(N, K // 128, dtype=torch.int32, device=DEV))
+           for N, K, _ in layer]
+
+    def repack(i):
+        for parts, (packed, meta) in zip(src[i % nl], dst):
+            col = 0
+            for qw, qz, sc in parts:
+                ops.awq_repack(qw, qz, sc, packed, meta, col)
+                col += sc.shape[1]
+
+    for i in range(3):
+        repack(i)
+    ts = [timed(lambda: repack(i)) for i in range(iters)]
+    torch.cuda.synchronize()
+    us = med(ts)
+    print(f"awq_repack, one 8B layer (7 launches, {src_bytes / 2 ** 20:.1f} "
+          f"MiB read): {us:.1f} us, {src_bytes / us / 1e3:.1f} GB/s read; "
+          f"32 layers {32 * us / 1e3:.2f} ms")
+    print(json.dumps({"awq_repack_layer_us": us}))
+
+
 def e2e(model_name, rounds):
     from resilient_llm_amd.engine import LLMEngine, PagedKVCache, SamplingParams
     from resilient_llm_amd.engine.graph import install_graph_runner
@@ -156,6 +264,8 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--splitk", type=int, default=0)
     ap.add_argument("--e2e", action="store_true")
+    ap.add_argument("--zp", action="store_true",
+                    help="the zero-point (AWQ) kernels and the repack")
     ap.add_argument("--model", default="llama-3-8b")
     ap.add_argument("--rounds", type=int, default=2)
     args = ap.parse_args()
@@ -163,6 +273,8 @@ def main():
     ops.load_extension(required=True)
     if args.e2e:
         e2e(args.model, args.rounds)
+    elif args.zp:
+        kernel_level_zp(args.iters, args.splitk)
     else:
         kernel_level(args.iters, args.splitk)
 
