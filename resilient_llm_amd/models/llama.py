@@ -141,10 +141,18 @@ class LlamaForCausalLM:
         # gate_up, down) — symmetric group-128 int4 weights, quantized
         # round-to-nearest at load, bf16 activations; lm_head, embed and
         # the norms stay bf16.  Up to 64 rows run the fused HIP GEMM
-        # (ops.w4a16_linear); more rows dequantize one projection at a
-        # time into a shared scratch buffer and take the bf16 GEMM.
+        # (ops.w4a16_linear), 65..256 rows its tiled form
+        # (ops.w4a16_tiled_linear: the decode batches the graph buckets
+        # go up to, mixed chunked-prefill and spec_lookup steps; a shape
+        # measured slower there stops lower, _W4_TILED_ROWS_BY_SHAPE); more
+        # rows dequantize one projection at a time into a shared scratch
+        # buffer and take the bf16 GEMM.  So does every whole-prompt
+        # prefill step (forward_prefill) above 64 rows, as it always did:
+        # the tiled form is the path of decode, mixed and verification
+        # steps, and what prefill computes stays what it was.
         # quant="int4-awq": the int4 path with a per-group zero-point and fp16
-        # scales (ops.w4a16_zp_linear / ops.w4_zp_dequant), the form
+        # scales (ops.w4a16_zp_linear / ops.w4a16_zp_tiled_linear /
+        # ops.w4_zp_dequant, routed by rows in the same way), the form
         # AutoAWQ checkpoints hold: load_safetensors repacks their
         # tensors on the device (ops.awq_repack); random init quantizes
         # asymmetric min/max round-to-nearest.  (A mode of the int4 path,
@@ -186,6 +194,7 @@ class LlamaForCausalLM:
         self.lora_slices: dict[str, list] = {}
         self._w4_scratch: Optional[torch.Tensor] = None
         self._w4_slab: Optional[torch.Tensor] = None
+        self._w4_tiled = True       # False inside forward_prefill
         self._init_weights(seed)
         if self.quant == "fp8":
             self._quantize_weights()
@@ -277,6 +286,16 @@ class LlamaForCausalLM:
         return _ref.scaled_mm_ref(x8, xs, w8, ws)
 
     _W4_FUSED_ROWS = 64         # ops.w4a16_linear takes 1..64 rows
+    _W4_TILED_ROWS = 256        # ops.w4a16_tiled_linear takes 65..256
+    # (N, K) whose tiled launch was measured slower than dequantize + GEMM
+    # above these rows (profiles/w4a16_tiled.md): the 8B qkv from 160 rows
+    _W4_TILED_ROWS_BY_SHAPE = {(6144, 4096): 128}
+
+    def _w4_tiled_rows(self, N: int, K: int) -> int:
+        if not self._w4_tiled:
+            return self._W4_FUSED_ROWS
+        return min(self._W4_TILED_ROWS,
+                   self._W4_TILED_ROWS_BY_SHAPE.get((N, K), 256))
 
     def _w4_shapes(self) -> dict:
         """Per-rank (after TP sharding) [N, K] of the int4 projections."""
@@ -332,9 +351,10 @@ class LlamaForCausalLM:
                 max(N * K for N, K in shapes.values()),
                 dtype=torch.bfloat16, device=self.device)
             self._w4_slab = torch.empty(
-                max(ops.w4a16_plan(N, K)[0] * N for N, K in shapes.values())
-                * self._W4_FUSED_ROWS, dtype=torch.float32,
-                device=self.device)
+                max(max(ops.w4a16_plan(N, K)[0] * self._W4_FUSED_ROWS,
+                        ops.w4a16_tiled_plan(N, K)[0] * self._W4_TILED_ROWS)
+                    * N for N, K in shapes.values()),
+                dtype=torch.float32, device=self.device)
 
     def _linear_w4(self, x: torch.Tensor, name: str) -> torch.Tensor:
         q4 = self.params[name + ".q4"]
@@ -345,6 +365,8 @@ class LlamaForCausalLM:
             if x.shape[0] <= self._W4_FUSED_ROWS:
                 return ops.w4a16_zp_linear(x, q4, m4, ws=self._w4_slab)
             N, K = m4.shape[0], x.shape[1]
+            if x.shape[0] <= self._w4_tiled_rows(N, K):
+                return ops.w4a16_zp_tiled_linear(x, q4, m4, ws=self._w4_slab)
             w = ops.w4_zp_dequant(
                 q4, m4, out=self._w4_scratch[:N * K].view(N, K))
             return _linear(x, w)
@@ -354,6 +376,8 @@ class LlamaForCausalLM:
         if x.shape[0] <= self._W4_FUSED_ROWS:
             return ops.w4a16_linear(x, q4, s4, ws=self._w4_slab)
         N, K = s4.shape[0], x.shape[1]
+        if x.shape[0] <= self._w4_tiled_rows(N, K):
+            return ops.w4a16_tiled_linear(x, q4, s4, ws=self._w4_slab)
         w = ops.w4_dequant(q4, s4, out=self._w4_scratch[:N * K].view(N, K))
         return _linear(x, w)
 
@@ -799,9 +823,15 @@ class LlamaForCausalLM:
             return ops.prefill_attn_qkv(qkv, cu_seqlens, self.scale,
                                         self.n_heads, self.n_kv_heads,
                                         self.config.head_dim)
-        return self._forward(input_ids, positions, kv_cache, slot_mapping,
-                             attn, last_idx=cu_seqlens[1:].long() - 1,
-                             adapter_idx=adapter_idx)
+        # int4: a whole-prompt prefill keeps dequantize + GEMM above 64 rows
+        self._w4_tiled = False
+        try:
+            return self._forward(input_ids, positions, kv_cache,
+                                 slot_mapping, attn,
+                                 last_idx=cu_seqlens[1:].long() - 1,
+                                 adapter_idx=adapter_idx)
+        finally:
+            self._w4_tiled = True
 
     def forward_mixed(self, input_ids: torch.Tensor, positions: torch.Tensor,
                       kv_cache, slot_mapping: torch.Tensor, n_decode: int,

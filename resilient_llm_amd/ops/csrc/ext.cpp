@@ -754,6 +754,83 @@ void w4a16_zp_linear_(const Tensor& x, const Tensor& packed,
   w4a16_linear_any(x, packed, meta, splitk, out, ws_opt, true);
 }
 
+// the K-slicing w4a16_tiled_linear runs with: [slices, k per slice]
+std::vector<int64_t> w4a16_tiled_plan(int64_t N, int64_t K, int64_t splitk) {
+  TORCH_CHECK(N >= 64 && N % 64 == 0 && K >= 128 && K % 128 == 0 &&
+              N < (int64_t(1) << 24) && K < (int64_t(1) << 22),
+              "w4a16_tiled needs N % 64 == 0 and K % 128 == 0");
+  int sk = 1, gps = 1;
+  rlli::w4a16_tiled_plan(int(N), int(K), int(splitk), &sk, &gps);
+  return {sk, int64_t(gps) * 128};
+}
+
+// The tiled forms, 1 <= M <= 256: out / ws as w4a16_linear_any.
+void w4a16_tiled_linear_any(const Tensor& x, const Tensor& packed,
+                            const Tensor& s, int64_t splitk, Tensor out,
+                            const c10::optional<Tensor>& ws_opt, bool zp) {
+  check_bf16_contig(x, "x");
+  check_bf16_contig(out, "out");
+  TORCH_CHECK(x.dim() == 2, "x must be [M, K]");
+  check_w4(packed, s, x, zp);
+  const int M = int(x.size(0));
+  const int K = int(x.size(1));
+  const int N = int(s.size(0));
+  TORCH_CHECK(M >= 1 && M <= 256,
+              "w4a16_tiled_linear needs 1 <= M <= 256, got ", M);
+  TORCH_CHECK(K % 128 == 0 && K >= 128,
+              "w4a16_tiled_linear needs K % 128 == 0, got K=", K);
+  // byte offsets of the 256 rows a full workgroup addresses stay in an int
+  TORCH_CHECK(x.size(1) < (int64_t(1) << 22), "K too large: ", x.size(1));
+  TORCH_CHECK(s.size(1) * 128 == K, "x/s K mismatch: x has K=", K,
+              ", s has ", s.size(1), " groups");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "x must be 16-byte aligned");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == M && out.size(1) == N &&
+              out.device() == x.device(), "out must be [M, N] = [", M, ", ",
+              N, "] on x's device");
+  int sk = 1, gps = 1;
+  rlli::w4a16_tiled_plan(N, K, int(splitk), &sk, &gps);
+  Tensor ws;
+  float* ws_ptr = nullptr;
+  if (sk > 1) {
+    if (ws_opt.has_value()) {
+      ws = *ws_opt;
+      TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.is_contiguous() &&
+                  ws.device() == x.device() &&
+                  ws.numel() >= int64_t(sk) * M * N,
+                  "ws must be contiguous f32 with >= slices*M*N = ",
+                  int64_t(sk) * M * N, " elements on x's device");
+    } else {
+      ws = at::empty({sk, M, N}, x.options().dtype(at::kFloat));
+    }
+    ws_ptr = ws.data_ptr<float>();
+  }
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  const auto* pk = reinterpret_cast<const uint32_t*>(packed.data_ptr());
+  if (zp) {
+    rlli::launch_w4a16_zp_tiled(
+        bf16_ptr(x), pk, reinterpret_cast<const uint32_t*>(s.data_ptr()),
+        ws_ptr, bf16_ptr(out), M, N, K, sk, gps, current_stream(x));
+  } else {
+    rlli::launch_w4a16_tiled(bf16_ptr(x), pk, bf16_ptr(s), ws_ptr,
+                             bf16_ptr(out), M, N, K, sk, gps,
+                             current_stream(x));
+  }
+  check_launch(zp ? "w4a16_zp_tiled_linear" : "w4a16_tiled_linear");
+}
+
+void w4a16_tiled_linear_(const Tensor& x, const Tensor& packed,
+                         const Tensor& s, int64_t splitk, Tensor out,
+                         const c10::optional<Tensor>& ws_opt) {
+  w4a16_tiled_linear_any(x, packed, s, splitk, out, ws_opt, false);
+}
+
+void w4a16_zp_tiled_linear_(const Tensor& x, const Tensor& packed,
+                            const Tensor& meta, int64_t splitk, Tensor out,
+                            const c10::optional<Tensor>& ws_opt) {
+  w4a16_tiled_linear_any(x, packed, meta, splitk, out, ws_opt, true);
+}
+
 void w4_dequant_(const Tensor& packed, const Tensor& s, Tensor out) {
   check_bf16_contig(out, "out");
   check_w4(packed, s, out);
@@ -1233,6 +1310,12 @@ TORCH_LIBRARY(rlli, m) {
   m.def("w4_zp_dequant_(Tensor packed, Tensor meta, Tensor(a!) out) -> ()");
   m.def("awq_repack_(Tensor qweight, Tensor qzeros, Tensor scales, "
         "Tensor(a!) packed, Tensor(b!) meta, int col_offset) -> ()");
+  m.def("w4a16_tiled_linear_(Tensor x, Tensor packed, Tensor s, int splitk, "
+        "Tensor(a!) out, Tensor(b!)? ws) -> ()");
+  m.def("w4a16_zp_tiled_linear_(Tensor x, Tensor packed, Tensor meta, "
+        "int splitk, Tensor(a!) out, Tensor(b!)? ws) -> ()");
+  m.def("w4a16_tiled_plan(int N, int K, int splitk) -> int[]",
+        &w4a16_tiled_plan);
   m.def("stream_probe(Tensor w, int splitk) -> Tensor");
   m.def("prefill_paged_attn(Tensor qkv, Tensor k_cache, Tensor v_cache, "
         "Tensor chunk_row0, Tensor chunk_pos0, Tensor chunk_nrows, "
@@ -1272,6 +1355,8 @@ TORCH_LIBRARY_IMPL(rlli, CUDA, m) {
   m.impl("w4a16_zp_linear_", &w4a16_zp_linear_);
   m.impl("w4_zp_dequant_", &w4_zp_dequant_);
   m.impl("awq_repack_", &awq_repack_);
+  m.impl("w4a16_tiled_linear_", &w4a16_tiled_linear_);
+  m.impl("w4a16_zp_tiled_linear_", &w4a16_zp_tiled_linear_);
   m.impl("stream_probe", &stream_probe);
   m.impl("prefill_paged_attn", &prefill_paged_attn);
   m.impl("kv_copy_blocks_", &kv_copy_blocks_);

@@ -179,6 +179,21 @@ void launch_awq_repack(const uint32_t* qweight, const uint32_t* qzeros,
                        const uint16_t* scales, uint32_t* packed,
                        uint32_t* meta, int N, int K, int col_offset,
                        hipStream_t stream);
+// Tiled forms (w4a16_tiled.hip): the same contract and tensors for
+// 1 <= M <= 256, one workgroup of ceil(M / 64) waves per 64-column panel x
+// K-slice with the packed weight staged once through LDS.
+// w4a16_tiled_plan is their slicing (whole groups, a function of N and K
+// only, no empty slice); ws is the [splitk, M, N] f32 slab when splitk > 1.
+void w4a16_tiled_plan(int N, int K, int splitk_req, int* splitk,
+                      int* grp_per_slice);
+void launch_w4a16_tiled(const uint16_t* x, const uint32_t* packed,
+                        const uint16_t* s, float* ws, uint16_t* out, int M,
+                        int N, int K, int splitk, int grp_per_slice,
+                        hipStream_t stream);
+void launch_w4a16_zp_tiled(const uint16_t* x, const uint32_t* packed,
+                           const uint32_t* meta, float* ws, uint16_t* out,
+                           int M, int N, int K, int splitk, int grp_per_slice,
+                           hipStream_t stream);
 
 void launch_skinny_gemm(const uint16_t* x, const uint16_t* w, float* ws,
                         uint16_t* out, int M, int N, int K, int splitk,
