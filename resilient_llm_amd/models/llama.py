@@ -144,7 +144,9 @@ class LlamaForCausalLM:
         # (ops.w4a16_linear), 65..256 rows its tiled form
         # (ops.w4a16_tiled_linear: the decode batches the graph buckets
         # go up to, mixed chunked-prefill and spec_lookup steps; a shape
-        # measured slower there stops lower, _W4_TILED_ROWS_BY_SHAPE); more
+        # measured slower there stops lower, _W4_TILED_ROWS_BY_SHAPE); the
+        # shapes and rows of _W4_WIDE_ROWS_BY_SHAPE, up to 512, run the
+        # wide form (ops.w4a16_wide_linear) in those steps instead; more
         # rows dequantize one projection at a time into a shared scratch
         # buffer and take the bf16 GEMM.  So does every whole-prompt
         # prefill step (forward_prefill) above 64 rows, as it always did:
@@ -297,6 +299,17 @@ class LlamaForCausalLM:
         return min(self._W4_TILED_ROWS,
                    self._W4_TILED_ROWS_BY_SHAPE.get((N, K), 256))
 
+    # (N, K): (first row, last row) that run ops.w4a16_wide_linear, ahead
+    # of the tiled op and of dequantize + GEMM: only the shapes and rows
+    # where it measured not slower than the path it replaces
+    # (profiles/w4a16_wide.md).  Any other shape keeps the routing above.
+    _W4_WIDE_ROWS_BY_SHAPE = {(28672, 4096): (224, 256),
+                              (4096, 14336): (224, 256)}
+
+    def _w4_wide(self, rows: int, N: int, K: int) -> bool:
+        first, last = self._W4_WIDE_ROWS_BY_SHAPE.get((N, K), (1, 0))
+        return self._w4_tiled and first <= rows <= last
+
     def _w4_shapes(self) -> dict:
         """Per-rank (after TP sharding) [N, K] of the int4 projections."""
         c = self.config
@@ -350,10 +363,14 @@ class LlamaForCausalLM:
             self._w4_scratch = torch.empty(
                 max(N * K for N, K in shapes.values()),
                 dtype=torch.bfloat16, device=self.device)
+            def slab_rows(N, K):           # slices * rows, per launch form
+                wide = self._W4_WIDE_ROWS_BY_SHAPE.get((N, K))
+                return max(
+                    ops.w4a16_plan(N, K)[0] * self._W4_FUSED_ROWS,
+                    ops.w4a16_tiled_plan(N, K)[0] * self._W4_TILED_ROWS,
+                    ops.w4a16_wide_plan(N, K)[0] * wide[1] if wide else 0)
             self._w4_slab = torch.empty(
-                max(max(ops.w4a16_plan(N, K)[0] * self._W4_FUSED_ROWS,
-                        ops.w4a16_tiled_plan(N, K)[0] * self._W4_TILED_ROWS)
-                    * N for N, K in shapes.values()),
+                max(slab_rows(N, K) * N for N, K in shapes.values()),
                 dtype=torch.float32, device=self.device)
 
     def _linear_w4(self, x: torch.Tensor, name: str) -> torch.Tensor:
@@ -365,6 +382,8 @@ class LlamaForCausalLM:
             if x.shape[0] <= self._W4_FUSED_ROWS:
                 return ops.w4a16_zp_linear(x, q4, m4, ws=self._w4_slab)
             N, K = m4.shape[0], x.shape[1]
+            if self._w4_wide(x.shape[0], N, K):
+                return ops.w4a16_zp_wide_linear(x, q4, m4, ws=self._w4_slab)
             if x.shape[0] <= self._w4_tiled_rows(N, K):
                 return ops.w4a16_zp_tiled_linear(x, q4, m4, ws=self._w4_slab)
             w = ops.w4_zp_dequant(
@@ -376,6 +395,8 @@ class LlamaForCausalLM:
         if x.shape[0] <= self._W4_FUSED_ROWS:
             return ops.w4a16_linear(x, q4, s4, ws=self._w4_slab)
         N, K = s4.shape[0], x.shape[1]
+        if self._w4_wide(x.shape[0], N, K):
+            return ops.w4a16_wide_linear(x, q4, s4, ws=self._w4_slab)
         if x.shape[0] <= self._w4_tiled_rows(N, K):
             return ops.w4a16_tiled_linear(x, q4, s4, ws=self._w4_slab)
         w = ops.w4_dequant(q4, s4, out=self._w4_scratch[:N * K].view(N, K))

@@ -592,4 +592,68 @@ def w4a16_tiled_plan(N: int, K: int, splitk: int = 0) -> tuple[int, int]:
     return int(sk), int(kps)
 
 
+def w4a16_wide_linear(x: torch.Tensor, packed: torch.Tensor,
+                      s: torch.Tensor, splitk: int = 0,
+                      out: torch.Tensor | None = None,
+                      ws: torch.Tensor | None = None) -> torch.Tensor:
+    """``w4a16_linear`` for 1 <= M <= 512 rows (mixed steps past the 256
+    of the tiled op): out[m, n] = bf16(sum_g s[n, g] * sum_{k in g}
+    x[m, k] * q[n, k]) on the same ``packed`` / ``s`` tensors (K % 128 ==
+    0, N % 128 == 0).  One workgroup of four waves per 128-column panel x
+    128-row block x K-slice converts the packed weight to bf16 once, on
+    its way into LDS; no bf16 weight is written to memory.  The scale
+    multiplies the group's f32 partial sum, as in ``w4a16_linear``.  Row m
+    depends on row m of x only; the K-slicing (``w4a16_wide_plan``;
+    ``splitk`` <= 0 picks it) depends on (N, K) only, so a row's bits do
+    not depend on M; no atomics.  ``out`` [M, N] bf16 is written in full
+    and nothing else is, apart from the split-K slab: the first
+    slices*M*N floats of ``ws`` when given, else a tensor the op
+    allocates — with ``out`` and ``ws`` given it allocates nothing."""
+    if x.is_cuda:
+        _gpu()
+        if out is None:
+            out = torch.empty((x.shape[0], s.shape[0]), dtype=x.dtype,
+                              device=x.device)
+        torch.ops.rlli.w4a16_wide_linear_(x, packed, s, splitk, out, ws)
+        return out
+    y = ref.w4a16_linear(x, packed, s)
+    if out is None:
+        return y
+    out.copy_(y)
+    return out
+
+
+def w4a16_zp_wide_linear(x: torch.Tensor, packed: torch.Tensor,
+                         meta: torch.Tensor, splitk: int = 0,
+                         out: torch.Tensor | None = None,
+                         ws: torch.Tensor | None = None) -> torch.Tensor:
+    """``w4a16_wide_linear`` for zero-point (AWQ) weights: out[m, n] =
+    bf16(sum_g s[n, g] * sum_{k in g} x[m, k] * (u[n, k] - z[n, g])) on
+    the ``packed`` / ``meta`` tensors of ``w4a16_zp_linear``, 1 <= M <=
+    512.  Shapes, slicing, ``out`` / ``ws`` and the row contract are those
+    of ``w4a16_wide_linear``."""
+    if x.is_cuda:
+        _gpu()
+        if out is None:
+            out = torch.empty((x.shape[0], meta.shape[0]), dtype=x.dtype,
+                              device=x.device)
+        torch.ops.rlli.w4a16_zp_wide_linear_(x, packed, meta, splitk, out,
+                                             ws)
+        return out
+    y = ref.w4a16_zp_linear(x, packed, meta)
+    if out is None:
+        return y
+    out.copy_(y)
+    return out
+
+
+def w4a16_wide_plan(N: int, K: int, splitk: int = 0) -> tuple[int, int]:
+    """(slices, k per slice) the wide ops run with on the GPU: K is cut
+    in whole 128-k groups, ceil(groups / slices) per slice, no empty
+    slice; a function of (N, K) only."""
+    _gpu()
+    sk, kps = torch.ops.rlli.w4a16_wide_plan(N, K, splitk)
+    return int(sk), int(kps)
+
+
 build_cos_sin = ref.build_cos_sin

@@ -50,6 +50,7 @@ SOURCES = [
     "w4a16.hip",
     "w4a16_zp.hip",
     "w4a16_tiled.hip",
+    "w4a16_wide.hip",
     "streamprobe.hip",
 ]
 HEADERS = ["common.h", "kernels.h", "sampling_common.h", "w4a16_common.h"]
@@ -65,6 +66,7 @@ EXTRA_FLAGS = {
     "decode_attn_shared.hip": _NO_PK_F32,
     "w4a16_zp.hip": _NO_PK_F32,
     "w4a16_tiled.hip": _NO_PK_F32,
+    "w4a16_wide.hip": _NO_PK_F32,
 }
 
 

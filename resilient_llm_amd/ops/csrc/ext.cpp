@@ -754,20 +754,51 @@ void w4a16_zp_linear_(const Tensor& x, const Tensor& packed,
   w4a16_linear_any(x, packed, meta, splitk, out, ws_opt, true);
 }
 
-// the K-slicing w4a16_tiled_linear runs with: [slices, k per slice]
-std::vector<int64_t> w4a16_tiled_plan(int64_t N, int64_t K, int64_t splitk) {
-  TORCH_CHECK(N >= 64 && N % 64 == 0 && K >= 128 && K % 128 == 0 &&
-              N < (int64_t(1) << 24) && K < (int64_t(1) << 22),
-              "w4a16_tiled needs N % 64 == 0 and K % 128 == 0");
+// The forms past 64 rows: the tiled ops (1 <= M <= 256, N % 64 == 0) and
+// the wide ops (1 <= M <= 512, N % 128 == 0) share their checks.
+struct W4RowsForm {
+  const char* name;        // of the symmetric op; "_zp" goes after "w4a16"
+  int max_rows, n_mult;
+  int k_bits;              // K < 2^k_bits: a workgroup's x byte offsets fit
+  void (*plan)(int, int, int, int*, int*);
+  decltype(&rlli::launch_w4a16_tiled) launch;
+  decltype(&rlli::launch_w4a16_zp_tiled) launch_zp;
+};
+const W4RowsForm kW4Tiled = {"w4a16_tiled", 256, 64, 22,
+                             &rlli::w4a16_tiled_plan,
+                             &rlli::launch_w4a16_tiled,
+                             &rlli::launch_w4a16_zp_tiled};
+const W4RowsForm kW4Wide = {"w4a16_wide", 512, 128, 21,
+                            &rlli::w4a16_wide_plan, &rlli::launch_w4a16_wide,
+                            &rlli::launch_w4a16_zp_wide};
+
+// the K-slicing a form runs with: [slices, k per slice]
+std::vector<int64_t> w4a16_rows_plan(const W4RowsForm& f, int64_t N,
+                                     int64_t K, int64_t splitk) {
+  TORCH_CHECK(N >= f.n_mult && N % f.n_mult == 0 && K >= 128 &&
+              K % 128 == 0 && N < (int64_t(1) << 24) &&
+              K < (int64_t(1) << f.k_bits),
+              f.name, " needs N % ", f.n_mult, " == 0 and K % 128 == 0");
   int sk = 1, gps = 1;
-  rlli::w4a16_tiled_plan(int(N), int(K), int(splitk), &sk, &gps);
+  f.plan(int(N), int(K), int(splitk), &sk, &gps);
   return {sk, int64_t(gps) * 128};
 }
 
-// The tiled forms, 1 <= M <= 256: out / ws as w4a16_linear_any.
-void w4a16_tiled_linear_any(const Tensor& x, const Tensor& packed,
-                            const Tensor& s, int64_t splitk, Tensor out,
-                            const c10::optional<Tensor>& ws_opt, bool zp) {
+std::vector<int64_t> w4a16_tiled_plan(int64_t N, int64_t K, int64_t splitk) {
+  return w4a16_rows_plan(kW4Tiled, N, K, splitk);
+}
+
+std::vector<int64_t> w4a16_wide_plan(int64_t N, int64_t K, int64_t splitk) {
+  return w4a16_rows_plan(kW4Wide, N, K, splitk);
+}
+
+// out / ws as w4a16_linear_any.
+void w4a16_rows_linear_any(const W4RowsForm& f, const Tensor& x,
+                           const Tensor& packed, const Tensor& s,
+                           int64_t splitk, Tensor out,
+                           const c10::optional<Tensor>& ws_opt, bool zp) {
+  const std::string op = std::string(zp ? "w4a16_zp" : "w4a16") +
+                         (f.name + 5) + "_linear";
   check_bf16_contig(x, "x");
   check_bf16_contig(out, "out");
   TORCH_CHECK(x.dim() == 2, "x must be [M, K]");
@@ -775,12 +806,15 @@ void w4a16_tiled_linear_any(const Tensor& x, const Tensor& packed,
   const int M = int(x.size(0));
   const int K = int(x.size(1));
   const int N = int(s.size(0));
-  TORCH_CHECK(M >= 1 && M <= 256,
-              "w4a16_tiled_linear needs 1 <= M <= 256, got ", M);
+  TORCH_CHECK(M >= 1 && M <= f.max_rows, f.name, "_linear needs 1 <= M <= ",
+              f.max_rows, ", got ", M);
+  TORCH_CHECK(N % f.n_mult == 0, f.name, "_linear needs N % ", f.n_mult,
+              " == 0, got N=", N);
   TORCH_CHECK(K % 128 == 0 && K >= 128,
-              "w4a16_tiled_linear needs K % 128 == 0, got K=", K);
-  // byte offsets of the 256 rows a full workgroup addresses stay in an int
-  TORCH_CHECK(x.size(1) < (int64_t(1) << 22), "K too large: ", x.size(1));
+              f.name, "_linear needs K % 128 == 0, got K=", K);
+  // byte offsets of the rows a full workgroup addresses stay in an int
+  TORCH_CHECK(x.size(1) < (int64_t(1) << f.k_bits), "K too large: ",
+              x.size(1));
   TORCH_CHECK(s.size(1) * 128 == K, "x/s K mismatch: x has K=", K,
               ", s has ", s.size(1), " groups");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
@@ -789,7 +823,7 @@ void w4a16_tiled_linear_any(const Tensor& x, const Tensor& packed,
               out.device() == x.device(), "out must be [M, N] = [", M, ", ",
               N, "] on x's device");
   int sk = 1, gps = 1;
-  rlli::w4a16_tiled_plan(N, K, int(splitk), &sk, &gps);
+  f.plan(N, K, int(splitk), &sk, &gps);
   Tensor ws;
   float* ws_ptr = nullptr;
   if (sk > 1) {
@@ -808,27 +842,38 @@ void w4a16_tiled_linear_any(const Tensor& x, const Tensor& packed,
   c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   const auto* pk = reinterpret_cast<const uint32_t*>(packed.data_ptr());
   if (zp) {
-    rlli::launch_w4a16_zp_tiled(
-        bf16_ptr(x), pk, reinterpret_cast<const uint32_t*>(s.data_ptr()),
-        ws_ptr, bf16_ptr(out), M, N, K, sk, gps, current_stream(x));
+    f.launch_zp(bf16_ptr(x), pk,
+                reinterpret_cast<const uint32_t*>(s.data_ptr()), ws_ptr,
+                bf16_ptr(out), M, N, K, sk, gps, current_stream(x));
   } else {
-    rlli::launch_w4a16_tiled(bf16_ptr(x), pk, bf16_ptr(s), ws_ptr,
-                             bf16_ptr(out), M, N, K, sk, gps,
-                             current_stream(x));
+    f.launch(bf16_ptr(x), pk, bf16_ptr(s), ws_ptr, bf16_ptr(out), M, N, K,
+             sk, gps, current_stream(x));
   }
-  check_launch(zp ? "w4a16_zp_tiled_linear" : "w4a16_tiled_linear");
+  check_launch(op.c_str());
 }
 
 void w4a16_tiled_linear_(const Tensor& x, const Tensor& packed,
                          const Tensor& s, int64_t splitk, Tensor out,
                          const c10::optional<Tensor>& ws_opt) {
-  w4a16_tiled_linear_any(x, packed, s, splitk, out, ws_opt, false);
+  w4a16_rows_linear_any(kW4Tiled, x, packed, s, splitk, out, ws_opt, false);
 }
 
 void w4a16_zp_tiled_linear_(const Tensor& x, const Tensor& packed,
                             const Tensor& meta, int64_t splitk, Tensor out,
                             const c10::optional<Tensor>& ws_opt) {
-  w4a16_tiled_linear_any(x, packed, meta, splitk, out, ws_opt, true);
+  w4a16_rows_linear_any(kW4Tiled, x, packed, meta, splitk, out, ws_opt, true);
+}
+
+void w4a16_wide_linear_(const Tensor& x, const Tensor& packed,
+                        const Tensor& s, int64_t splitk, Tensor out,
+                        const c10::optional<Tensor>& ws_opt) {
+  w4a16_rows_linear_any(kW4Wide, x, packed, s, splitk, out, ws_opt, false);
+}
+
+void w4a16_zp_wide_linear_(const Tensor& x, const Tensor& packed,
+                           const Tensor& meta, int64_t splitk, Tensor out,
+                           const c10::optional<Tensor>& ws_opt) {
+  w4a16_rows_linear_any(kW4Wide, x, packed, meta, splitk, out, ws_opt, true);
 }
 
 void w4_dequant_(const Tensor& packed, const Tensor& s, Tensor out) {
@@ -1316,6 +1361,12 @@ TORCH_LIBRARY(rlli, m) {
         "int splitk, Tensor(a!) out, Tensor(b!)? ws) -> ()");
   m.def("w4a16_tiled_plan(int N, int K, int splitk) -> int[]",
         &w4a16_tiled_plan);
+  m.def("w4a16_wide_linear_(Tensor x, Tensor packed, Tensor s, int splitk, "
+        "Tensor(a!) out, Tensor(b!)? ws) -> ()");
+  m.def("w4a16_zp_wide_linear_(Tensor x, Tensor packed, Tensor meta, "
+        "int splitk, Tensor(a!) out, Tensor(b!)? ws) -> ()");
+  m.def("w4a16_wide_plan(int N, int K, int splitk) -> int[]",
+        &w4a16_wide_plan);
   m.def("stream_probe(Tensor w, int splitk) -> Tensor");
   m.def("prefill_paged_attn(Tensor qkv, Tensor k_cache, Tensor v_cache, "
         "Tensor chunk_row0, Tensor chunk_pos0, Tensor chunk_nrows, "
@@ -1357,6 +1408,8 @@ TORCH_LIBRARY_IMPL(rlli, CUDA, m) {
   m.impl("awq_repack_", &awq_repack_);
   m.impl("w4a16_tiled_linear_", &w4a16_tiled_linear_);
   m.impl("w4a16_zp_tiled_linear_", &w4a16_zp_tiled_linear_);
+  m.impl("w4a16_wide_linear_", &w4a16_wide_linear_);
+  m.impl("w4a16_zp_wide_linear_", &w4a16_zp_wide_linear_);
   m.impl("stream_probe", &stream_probe);
   m.impl("prefill_paged_attn", &prefill_paged_attn);
   m.impl("kv_copy_blocks_", &kv_copy_blocks_);

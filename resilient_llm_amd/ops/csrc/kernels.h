@@ -194,6 +194,22 @@ void launch_w4a16_zp_tiled(const uint16_t* x, const uint32_t* packed,
                            const uint32_t* meta, float* ws, uint16_t* out,
                            int M, int N, int K, int splitk, int grp_per_slice,
                            hipStream_t stream);
+// Wide forms (w4a16_wide.hip): the same contract and tensors for
+// 1 <= M <= 512 and N % 128 == 0, one workgroup of four waves per
+// 128-column panel x 128-row block x K-slice, the weight converted to bf16
+// once per workgroup on its way into LDS.  w4a16_wide_plan is their
+// slicing (whole groups, a function of N and K only, no empty slice); ws
+// is the [splitk, M, N] f32 slab when splitk > 1.
+void w4a16_wide_plan(int N, int K, int splitk_req, int* splitk,
+                     int* grp_per_slice);
+void launch_w4a16_wide(const uint16_t* x, const uint32_t* packed,
+                       const uint16_t* s, float* ws, uint16_t* out, int M,
+                       int N, int K, int splitk, int grp_per_slice,
+                       hipStream_t stream);
+void launch_w4a16_zp_wide(const uint16_t* x, const uint32_t* packed,
+                          const uint32_t* meta, float* ws, uint16_t* out,
+                          int M, int N, int K, int splitk, int grp_per_slice,
+                          hipStream_t stream);
 
 void launch_skinny_gemm(const uint16_t* x, const uint16_t* w, float* ws,
                         uint16_t* out, int M, int N, int K, int splitk,
