@@ -288,6 +288,12 @@ class LlamaForCausalLM:
         return _ref.scaled_mm_ref(x8, xs, w8, ws)
 
     _W4_FUSED_ROWS = 64         # ops.w4a16_linear takes 1..64 rows
+    # up to these rows the down projection takes gu itself and applies
+    # SwiGLU in its A fragments (ops.w4a16_silu_linear, bit-identical to
+    # silu_mul + w4a16_linear).  0: it measured slower than that pair at
+    # every M on the 8B down shape (profiles/w4a16_silu.md), so no step
+    # routes to it
+    _W4_SILU_ROWS = 0
     _W4_TILED_ROWS = 256        # ops.w4a16_tiled_linear takes 65..256
     # (N, K) whose tiled launch was measured slower than dequantize + GEMM
     # above these rows (profiles/w4a16_tiled.md): the 8B qkv from 160 rows
@@ -401,6 +407,16 @@ class LlamaForCausalLM:
             return ops.w4a16_tiled_linear(x, q4, s4, ws=self._w4_slab)
         w = ops.w4_dequant(q4, s4, out=self._w4_scratch[:N * K].view(N, K))
         return _linear(x, w)
+
+    def _linear_w4_silu(self, gu: torch.Tensor, name: str) -> torch.Tensor:
+        """``_linear_w4(ops.silu_mul(gu), name)`` in one launch, for the
+        at most ``_W4_SILU_ROWS`` rows ``_layer_w4`` sends here."""
+        q4 = self.params[name + ".q4"]
+        if self.quant == "int4-awq":
+            return ops.w4a16_zp_silu_linear(gu, q4, self.params[name + ".m4"],
+                                            ws=self._w4_slab)
+        return ops.w4a16_silu_linear(gu, q4, self.params[name + ".s4"],
+                                     ws=self._w4_slab)
 
     def load_safetensors(self, path: str) -> int:
         """Load HF-Llama-named safetensors shards, TP-sharded at load
@@ -798,8 +814,11 @@ class LlamaForCausalLM:
         h = self._all_reduce(self._linear_w4(attn_out, f"l{i}.o"))
         h2 = ops.rmsnorm_residual_(h, residual, p[f"l{i}.ln2"], c.rms_eps)
         gu = self._linear_w4(h2, f"l{i}.gate_up")
-        mlp = self._all_reduce(self._linear_w4(ops.silu_mul(gu),
-                                               f"l{i}.down"))
+        if gu.is_cuda and gu.shape[0] <= self._W4_SILU_ROWS:
+            down = self._linear_w4_silu(gu, f"l{i}.down")
+        else:
+            down = self._linear_w4(ops.silu_mul(gu), f"l{i}.down")
+        mlp = self._all_reduce(down)
         return mlp, residual
 
     def _layer_lora(self, i: int, x: torch.Tensor,

@@ -496,6 +496,81 @@ def w4a16_zp_linear(x: torch.Tensor, packed: torch.Tensor,
     return out
 
 
+def _check_w4_silu_cpu(gu: torch.Tensor, sm: torch.Tensor, splitk: int,
+                       ws: torch.Tensor | None) -> None:
+    """What the device ops check about ``gu`` and ``ws``, for CPU tensors
+    (``sm`` is s or meta, [N, K/128])."""
+    N, G = sm.shape
+    K = G * ref.W4_GROUP
+    if gu.dtype != torch.bfloat16 or gu.dim() != 2 or gu.stride(1) != 1:
+        raise ValueError("gu must be bf16 [M, 2K] with unit inner stride")
+    M, width = gu.shape
+    if width % 2 or width != 2 * K:
+        raise ValueError(f"gu must be [M, 2K] = [M, {2 * K}], got width "
+                         f"{width}")
+    if not 1 <= M <= 64:
+        raise ValueError(f"w4a16_silu_linear needs 1 <= M <= 64, got {M}")
+    if ws is not None:
+        # w4a16_plan: whole groups per slice, no empty slice
+        panels = N // 64
+        sk = (min(splitk, G) if splitk > 0 else
+              min(max(1, -(-1024 // panels)), max(1, G // 4)))
+        slices = -(-G // -(-G // sk))
+        if slices > 1 and (ws.dtype != torch.float32
+                           or ws.numel() < slices * M * N):
+            raise ValueError(f"ws must be f32 with >= slices*M*N = "
+                             f"{slices * M * N} elements")
+
+
+def w4a16_silu_linear(gu: torch.Tensor, packed: torch.Tensor,
+                      s: torch.Tensor, splitk: int = 0,
+                      out: torch.Tensor | None = None,
+                      ws: torch.Tensor | None = None) -> torch.Tensor:
+    """SwiGLU fused into ``w4a16_linear`` (the int4 decode down
+    projection): out[m, n] = bf16(sum_g s[n, g] * sum_{k in g} a[m, k] *
+    q[n, k]) with a[m, k] = bf16(silu(gu[m, k]) * gu[m, K + k]) built in
+    the kernel's A fragments from ``gu`` [M, 2K] bf16, the packed gate|up
+    rows, 1 <= M <= 64.  Bit-identical to ``w4a16_linear(silu_mul(gu),
+    packed, s)`` for every M, without that launch and its [M, K]
+    intermediate; ``packed`` / ``s``, slicing, ``out`` / ``ws`` and the row
+    contract are those of ``w4a16_linear``."""
+    if gu.is_cuda:
+        _gpu()
+        if out is None:
+            out = torch.empty((gu.shape[0], s.shape[0]), dtype=gu.dtype,
+                              device=gu.device)
+        torch.ops.rlli.w4a16_silu_linear_(gu, packed, s, splitk, out, ws)
+        return out
+    _check_w4_silu_cpu(gu, s, splitk, ws)
+    y = ref.w4a16_silu_linear(gu, packed, s)
+    if out is None:
+        return y
+    out.copy_(y)
+    return out
+
+
+def w4a16_zp_silu_linear(gu: torch.Tensor, packed: torch.Tensor,
+                         meta: torch.Tensor, splitk: int = 0,
+                         out: torch.Tensor | None = None,
+                         ws: torch.Tensor | None = None) -> torch.Tensor:
+    """``w4a16_silu_linear`` for zero-point (AWQ) weights: bit-identical
+    to ``w4a16_zp_linear(silu_mul(gu), packed, meta)``."""
+    if gu.is_cuda:
+        _gpu()
+        if out is None:
+            out = torch.empty((gu.shape[0], meta.shape[0]), dtype=gu.dtype,
+                              device=gu.device)
+        torch.ops.rlli.w4a16_zp_silu_linear_(gu, packed, meta, splitk, out,
+                                             ws)
+        return out
+    _check_w4_silu_cpu(gu, meta, splitk, ws)
+    y = ref.w4a16_zp_silu_linear(gu, packed, meta)
+    if out is None:
+        return y
+    out.copy_(y)
+    return out
+
+
 def w4_zp_dequant(packed: torch.Tensor, meta: torch.Tensor,
                   out: torch.Tensor | None = None) -> torch.Tensor:
     """bf16 [N, K] = bf16(f32(s) * (u - z)) of a zero-point int4 weight,

@@ -49,6 +49,7 @@ SOURCES = [
     "skinny2.hip",
     "w4a16.hip",
     "w4a16_zp.hip",
+    "w4a16_silu.hip",
     "w4a16_tiled.hip",
     "w4a16_wide.hip",
     "streamprobe.hip",
@@ -65,6 +66,7 @@ EXTRA_FLAGS = {
     "sampling_nucleus.hip": _NO_PK_F32,
     "decode_attn_shared.hip": _NO_PK_F32,
     "w4a16_zp.hip": _NO_PK_F32,
+    "w4a16_silu.hip": _NO_PK_F32,
     "w4a16_tiled.hip": _NO_PK_F32,
     "w4a16_wide.hip": _NO_PK_F32,
 }

@@ -39,6 +39,17 @@ DEV_INLINE uint16_t f32_to_bf16(float x) {
   return uint16_t(u >> 16);
 }
 
+// SwiGLU on one (gate, up) pair of bf16: bf16(silu(f32(g)) * f32(u)).  The
+// one definition of this rounding: silu_mul.hip writes it to memory and
+// the fused int4 down projection (w4a16_silu.hip) builds its A fragments
+// from it, and the two must agree bit for bit.
+DEV_INLINE uint16_t silu_mul_bf16(uint16_t g, uint16_t u) {
+  const float gf = bf16_to_f32(g);
+  const float uf = bf16_to_f32(u);
+  const float s = gf / (1.f + __expf(-gf));
+  return f32_to_bf16(s * uf);
+}
+
 // ---- KV-cache element codecs --------------------------------------
 // The paged cache stores bf16 (default) or OCP fp8-e4m3 (opt-in,
 // `kv_dtype: fp8`): half the HBM traffic per token and double the

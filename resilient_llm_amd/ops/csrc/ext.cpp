@@ -691,21 +691,29 @@ std::vector<int64_t> w4a16_plan(int64_t N, int64_t K, int64_t splitk) {
 // first slices*M*N floats of the split-K slab: ``ws`` when the caller
 // owns one (>= that many f32), else a caching-allocator tensor, which
 // inside hipGraph capture comes from the graph's pool.
+// ``silu``: x is gu [M, 2K], the packed gate|up rows (w4a16_silu.hip).
 void w4a16_linear_any(const Tensor& x, const Tensor& packed, const Tensor& s,
                       int64_t splitk, Tensor out,
-                      const c10::optional<Tensor>& ws_opt, bool zp) {
-  check_bf16_contig(x, "x");
+                      const c10::optional<Tensor>& ws_opt, bool zp,
+                      bool silu = false) {
+  check_bf16_contig(x, silu ? "gu" : "x");
   check_bf16_contig(out, "out");
-  TORCH_CHECK(x.dim() == 2, "x must be [M, K]");
+  TORCH_CHECK(x.dim() == 2, silu ? "gu must be [M, 2K]" : "x must be [M, K]");
   check_w4(packed, s, x, zp);
   const int M = int(x.size(0));
-  const int K = int(x.size(1));
+  TORCH_CHECK(!silu || x.size(1) % 2 == 0,
+              "w4a16_silu_linear needs an even gu width, got ", x.size(1));
+  const int K = int(silu ? x.size(1) / 2 : x.size(1));
   const int N = int(s.size(0));
-  TORCH_CHECK(M >= 1 && M <= 64, "w4a16_linear needs 1 <= M <= 64, got ", M);
-  TORCH_CHECK(K % 128 == 0 && K >= 128,
-              "w4a16_linear needs K % 128 == 0, got K=", K);
+  const char* op = silu ? "w4a16_silu_linear" : "w4a16_linear";
+  TORCH_CHECK(M >= 1 && M <= 64, op, " needs 1 <= M <= 64, got ", M);
+  TORCH_CHECK(K % 128 == 0 && K >= 128, op, " needs K % 128 == 0, got K=",
+              K);
   TORCH_CHECK(s.size(1) * 128 == K, "x/s K mismatch: x has K=", K,
               ", s has ", s.size(1), " groups");
+  // the kernel's 32-bit byte offsets into gu
+  TORCH_CHECK(!silu || int64_t(M) * K * 4 < (int64_t(1) << 31),
+              "gu too large");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
               "x must be 16-byte aligned");
   TORCH_CHECK(out.dim() == 2 && out.size(0) == M && out.size(1) == N &&
@@ -731,15 +739,28 @@ void w4a16_linear_any(const Tensor& x, const Tensor& packed, const Tensor& s,
   c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   const auto* pk = reinterpret_cast<const uint32_t*>(packed.data_ptr());
   if (zp) {
-    rlli::launch_w4a16_zp(bf16_ptr(x), pk,
-                          reinterpret_cast<const uint32_t*>(s.data_ptr()),
-                          ws_ptr, bf16_ptr(out), M, N, K, sk, gps,
-                          current_stream(x));
+    (silu ? rlli::launch_w4a16_zp_silu : rlli::launch_w4a16_zp)(
+        bf16_ptr(x), pk, reinterpret_cast<const uint32_t*>(s.data_ptr()),
+        ws_ptr, bf16_ptr(out), M, N, K, sk, gps, current_stream(x));
   } else {
-    rlli::launch_w4a16(bf16_ptr(x), pk, bf16_ptr(s), ws_ptr, bf16_ptr(out),
-                       M, N, K, sk, gps, current_stream(x));
+    (silu ? rlli::launch_w4a16_silu : rlli::launch_w4a16)(
+        bf16_ptr(x), pk, bf16_ptr(s), ws_ptr, bf16_ptr(out), M, N, K, sk,
+        gps, current_stream(x));
   }
-  check_launch(zp ? "w4a16_zp_linear" : "w4a16_linear");
+  check_launch(silu ? (zp ? "w4a16_zp_silu_linear" : "w4a16_silu_linear")
+                    : (zp ? "w4a16_zp_linear" : "w4a16_linear"));
+}
+
+void w4a16_silu_linear_(const Tensor& gu, const Tensor& packed,
+                        const Tensor& s, int64_t splitk, Tensor out,
+                        const c10::optional<Tensor>& ws_opt) {
+  w4a16_linear_any(gu, packed, s, splitk, out, ws_opt, false, true);
+}
+
+void w4a16_zp_silu_linear_(const Tensor& gu, const Tensor& packed,
+                           const Tensor& meta, int64_t splitk, Tensor out,
+                           const c10::optional<Tensor>& ws_opt) {
+  w4a16_linear_any(gu, packed, meta, splitk, out, ws_opt, true, true);
 }
 
 void w4a16_linear_(const Tensor& x, const Tensor& packed, const Tensor& s,
@@ -1355,6 +1376,10 @@ TORCH_LIBRARY(rlli, m) {
   m.def("w4_zp_dequant_(Tensor packed, Tensor meta, Tensor(a!) out) -> ()");
   m.def("awq_repack_(Tensor qweight, Tensor qzeros, Tensor scales, "
         "Tensor(a!) packed, Tensor(b!) meta, int col_offset) -> ()");
+  m.def("w4a16_silu_linear_(Tensor gu, Tensor packed, Tensor s, int splitk, "
+        "Tensor(a!) out, Tensor(b!)? ws) -> ()");
+  m.def("w4a16_zp_silu_linear_(Tensor gu, Tensor packed, Tensor meta, "
+        "int splitk, Tensor(a!) out, Tensor(b!)? ws) -> ()");
   m.def("w4a16_tiled_linear_(Tensor x, Tensor packed, Tensor s, int splitk, "
         "Tensor(a!) out, Tensor(b!)? ws) -> ()");
   m.def("w4a16_zp_tiled_linear_(Tensor x, Tensor packed, Tensor meta, "
@@ -1406,6 +1431,8 @@ TORCH_LIBRARY_IMPL(rlli, CUDA, m) {
   m.impl("w4a16_zp_linear_", &w4a16_zp_linear_);
   m.impl("w4_zp_dequant_", &w4_zp_dequant_);
   m.impl("awq_repack_", &awq_repack_);
+  m.impl("w4a16_silu_linear_", &w4a16_silu_linear_);
+  m.impl("w4a16_zp_silu_linear_", &w4a16_zp_silu_linear_);
   m.impl("w4a16_tiled_linear_", &w4a16_tiled_linear_);
   m.impl("w4a16_zp_tiled_linear_", &w4a16_zp_tiled_linear_);
   m.impl("w4a16_wide_linear_", &w4a16_wide_linear_);

@@ -179,6 +179,18 @@ void launch_awq_repack(const uint32_t* qweight, const uint32_t* qzeros,
                        const uint16_t* scales, uint32_t* packed,
                        uint32_t* meta, int N, int K, int col_offset,
                        hipStream_t stream);
+// SwiGLU-fused forms (w4a16_silu.hip): launch_w4a16 / launch_w4a16_zp with
+// gu [M, 2K] (packed gate|up rows) in place of x and the A fragment built
+// as bf16(silu(g) * u), the rounding launch_silu_mul stores: bit-identical
+// to that launch followed by the plain one, same slicing and slab.
+void launch_w4a16_silu(const uint16_t* gu, const uint32_t* packed,
+                       const uint16_t* s, float* ws, uint16_t* out, int M,
+                       int N, int K, int splitk, int grp_per_slice,
+                       hipStream_t stream);
+void launch_w4a16_zp_silu(const uint16_t* gu, const uint32_t* packed,
+                          const uint32_t* meta, float* ws, uint16_t* out,
+                          int M, int N, int K, int splitk, int grp_per_slice,
+                          hipStream_t stream);
 // Tiled forms (w4a16_tiled.hip): the same contract and tensors for
 // 1 <= M <= 256, one workgroup of ceil(M / 64) waves per 64-column panel x
 // K-slice with the packed weight staged once through LDS.

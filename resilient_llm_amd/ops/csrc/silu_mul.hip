@@ -24,12 +24,7 @@ DEV_INLINE void silu_mul_one(uint4 graw, uint4 uraw, uint16_t* dst) {
   g.u = graw;
   u.u = uraw;
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const float gf = bf16_to_f32(g.s[i]);
-    const float uf = bf16_to_f32(u.s[i]);
-    const float s = gf / (1.f + __expf(-gf));
-    o.s[i] = f32_to_bf16(s * uf);
-  }
+  for (int i = 0; i < 8; ++i) o.s[i] = silu_mul_bf16(g.s[i], u.s[i]);
   *reinterpret_cast<uint4*>(dst) = o.u;
 }
 

@@ -48,6 +48,19 @@ DEV_INLINE u32x4 nibbles_to_bf16(unsigned d) {
   return f;
 }
 
+// 8 (gate, up) bf16 pairs of one lane -> the A fragment of their SwiGLU
+DEV_INLINE u32x4 silu_mul_frag(u32x4 g, u32x4 u) {
+  u32x4 a;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const unsigned lo = silu_mul_bf16(uint16_t(g[p]), uint16_t(u[p]));
+    const unsigned hi = silu_mul_bf16(uint16_t(g[p] >> 16),
+                                      uint16_t(u[p] >> 16));
+    a[p] = lo | (hi << 16);
+  }
+  return a;
+}
+
 // One wave = one 64-column panel x one K-slice of whole groups.
 //  blockIdx.x = panel + n_panels * slice
 // GB = depth of the B ring in GROUPS (CT dwordx4 + CT scales each).  The
@@ -57,7 +70,13 @@ DEV_INLINE u32x4 nibbles_to_bf16(unsigned d) {
 // issued anyway, clamped to the last group of K (always in bounds), and
 // never consumed: the loop body has no load branch.
 // ZP: ``sm`` is meta u32 [N, G] instead of the bf16 scales [N, G].
-template <int M_TILES, int GB, bool ZP>
+// SILU (w4a16_silu.hip): ``x`` is gu [M, 2K], the packed gate|up rows, and
+// the A fragment is bf16(silu(g) * u).  Every ring slot then holds the
+// gate and the up octet (two loads where the plain form issues one, at
+// the same distance ahead) and the activation is computed on the slot's
+// registers right before the MFMAs that consume it; everything after the
+// A fragment is the plain kernel.
+template <int M_TILES, int GB, bool ZP, bool SILU = false>
 __global__ __launch_bounds__(64)
 void w4a16_kernel(const uint16_t* __restrict__ x,
                   const uint32_t* __restrict__ packed,
@@ -78,9 +97,12 @@ void w4a16_kernel(const uint16_t* __restrict__ x,
   const int koct = lane >> 4;   // k-octet: 8 contiguous k
 
   // x rows >= M are hardware-bounds-checked to 0 (padded M tiles add
-  // nothing); every packed / scale address is in bounds by construction.
+  // nothing: silu(0) * 0 = 0 too); every packed / scale address is in
+  // bounds by construction.
+  constexpr int AV = SILU ? 2 : 1;           // operands per A fragment
+  const int lda = AV * K;                    // row stride of x / gu
   const auto xrsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint16_t*>(x), (short)0, M * K * 2, 0x00020000);
+      const_cast<uint16_t*>(x), (short)0, M * lda * 2, 0x00020000);
   const auto wrsrc = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<uint32_t*>(packed), (short)0,
       int(int64_t(N) * K / 2), 0x00020000);
@@ -97,7 +119,7 @@ void w4a16_kernel(const uint16_t* __restrict__ x,
   int voff_a[M_TILES];
 #pragma unroll
   for (int mt = 0; mt < M_TILES; ++mt)
-    voff_a[mt] = ((mt * 16 + jcol) * K + koct * 8) * 2;
+    voff_a[mt] = ((mt * 16 + jcol) * lda + koct * 8) * 2;
 
   f32x4 acc[M_TILES][CT];
 #pragma unroll
@@ -108,7 +130,7 @@ void w4a16_kernel(const uint16_t* __restrict__ x,
   constexpr int AUX_NT = 2;                  // nontemporal policy
   u32x4 bq[GB][CT];
   std::conditional_t<ZP, unsigned, unsigned short> bs[GB][CT];
-  u32x4 abuf[GRAN][M_TILES];
+  u32x4 abuf[GRAN][M_TILES][AV];             // SILU: [0] gate, [1] up
 
   auto load_b = [&](int p, int g) {
     g = min(g, G - 1);                       // SGPR: g is wave-uniform
@@ -128,8 +150,10 @@ void w4a16_kernel(const uint16_t* __restrict__ x,
     g = min(g, G - 1);
 #pragma unroll
     for (int mt = 0; mt < M_TILES; ++mt)
-      abuf[j][mt] = __builtin_amdgcn_raw_buffer_load_b128(
-          xrsrc, voff_a[mt], (g * GROUP + j * 32) * 2, 0);
+#pragma unroll
+      for (int v = 0; v < AV; ++v)
+        abuf[j][mt][v] = __builtin_amdgcn_raw_buffer_load_b128(
+            xrsrc, voff_a[mt], (v * K + g * GROUP + j * 32) * 2, 0);
   };
 
   constexpr unsigned FIFTH = ZP ? BF16_ONE : BF16_NEG136;
@@ -150,7 +174,11 @@ void w4a16_kernel(const uint16_t* __restrict__ x,
         bfrag[ct] = as_bf16x8(nibbles_to_bf16(bq[p][ct][j]));
 #pragma unroll
       for (int mt = 0; mt < M_TILES; ++mt) {
-        const bf16x8_vec afrag = as_bf16x8(abuf[j][mt]);
+        bf16x8_vec afrag;
+        if constexpr (SILU)
+          afrag = as_bf16x8(silu_mul_frag(abuf[j][mt][0], abuf[j][mt][1]));
+        else
+          afrag = as_bf16x8(abuf[j][mt][0]);
         sacc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
             afrag, as_bf16x8(neg136), j ? sacc[mt] : zero, 0, 0, 0);
 #pragma unroll
@@ -280,7 +308,7 @@ void w4_dequant_kernel(const uint32_t* __restrict__ packed,
   }
 }
 
-template <bool ZP>
+template <bool ZP, bool SILU = false>
 void launch_w4a16_any(const uint16_t* x, const uint32_t* packed,
                       const void* sm, float* ws, uint16_t* out, int M, int N,
                       int K, int splitk, int grp_per_slice,
@@ -289,7 +317,7 @@ void launch_w4a16_any(const uint16_t* x, const uint32_t* packed,
   const int blocks = (N / BN) * splitk;
   auto launch = [&](auto mt_tag, auto gb_tag) {
     hipLaunchKernelGGL((w4a16_kernel<decltype(mt_tag)::value,
-                                     decltype(gb_tag)::value, ZP>),
+                                     decltype(gb_tag)::value, ZP, SILU>),
                        dim3(blocks), dim3(64), 0, stream, x, packed, sm, ws,
                        out, M, N, K, grp_per_slice, splitk);
   };

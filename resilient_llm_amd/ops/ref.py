@@ -626,6 +626,19 @@ def w4a16_zp_linear(x: torch.Tensor, packed: torch.Tensor,
     return (part * s.unsqueeze(0)).sum(dim=-1).to(x.dtype)
 
 
+def w4a16_silu_linear(gu: torch.Tensor, packed: torch.Tensor,
+                      s: torch.Tensor) -> torch.Tensor:
+    """SwiGLU + int4 down projection: ``w4a16_linear`` of ``silu_mul(gu)``,
+    the activation rounded to gu's dtype in between."""
+    return w4a16_linear(silu_mul(gu), packed, s)
+
+
+def w4a16_zp_silu_linear(gu: torch.Tensor, packed: torch.Tensor,
+                         meta: torch.Tensor) -> torch.Tensor:
+    """``w4a16_zp_linear`` of ``silu_mul(gu)``."""
+    return w4a16_zp_linear(silu_mul(gu), packed, meta)
+
+
 def w4_zp_dequant(packed: torch.Tensor, meta: torch.Tensor,
                   out: torch.Tensor | None = None) -> torch.Tensor:
     """bf16 [N, K] = bf16(f32(s) * (u - z)): one rounding per weight."""
