@@ -66,6 +66,9 @@ class LlamaConfig:
     # token ids that end generation (Llama-3: <|end_of_text|>=128001 and
     # <|eot_id|>=128009); overridable per deployment / by a real tokenizer
     eos_ids: tuple = (2,)
+    # Qwen3: a per-head RMSNorm on q and on k (weights [head_dim], shared by
+    # all heads) between the qkv projection and RoPE
+    qk_norm: bool = False
 
     @property
     def q_size(self) -> int:
@@ -97,6 +100,27 @@ MODEL_PRESETS: dict[str, LlamaConfig] = {
         name="mistral-7b", hidden_size=4096, n_layers=32, n_heads=32,
         n_kv_heads=8, head_dim=128, intermediate_size=14336,
         vocab_size=32768, rope_theta=1000000.0),
+    # Qwen3 dense family: q/k norm, head_dim independent of hidden_size /
+    # n_heads, tied embeddings at the small sizes.  Geometry written from
+    # memory of the published config.json files - no checkpoint was at hand
+    # to check it against; load_safetensors' shape checks make a wrong
+    # number fail at load.
+    "qwen3-0.6b": LlamaConfig(
+        name="qwen3-0.6b", hidden_size=1024, n_layers=28, n_heads=16,
+        n_kv_heads=8, head_dim=128, intermediate_size=3072,
+        vocab_size=151936, rope_theta=1000000.0, rms_eps=1e-6,
+        max_position=40960, tie_embeddings=True,
+        eos_ids=(151645, 151643), qk_norm=True),
+    "qwen3-8b": LlamaConfig(
+        name="qwen3-8b", hidden_size=4096, n_layers=36, n_heads=32,
+        n_kv_heads=8, head_dim=128, intermediate_size=12288,
+        vocab_size=151936, rope_theta=1000000.0, rms_eps=1e-6,
+        max_position=40960, eos_ids=(151645, 151643), qk_norm=True),
+    "qwen3-32b": LlamaConfig(
+        name="qwen3-32b", hidden_size=5120, n_layers=64, n_heads=64,
+        n_kv_heads=8, head_dim=128, intermediate_size=25600,
+        vocab_size=151936, rope_theta=1000000.0, rms_eps=1e-6,
+        max_position=40960, eos_ids=(151645, 151643), qk_norm=True),
     # CPU-testable models
     "tiny": LlamaConfig(
         name="tiny", hidden_size=256, n_layers=2, n_heads=4, n_kv_heads=2,
@@ -106,6 +130,15 @@ MODEL_PRESETS: dict[str, LlamaConfig] = {
         name="tiny-128", hidden_size=512, n_layers=2, n_heads=4, n_kv_heads=1,
         head_dim=128, intermediate_size=1024, vocab_size=512,
         max_position=2048),
+    # q/k-norm forms of the two above; tiny-qk has q_size (512) != hidden
+    "tiny-qk": LlamaConfig(
+        name="tiny-qk", hidden_size=256, n_layers=2, n_heads=8, n_kv_heads=2,
+        head_dim=64, intermediate_size=512, vocab_size=512,
+        max_position=2048, qk_norm=True),
+    "tiny-qk-128": LlamaConfig(
+        name="tiny-qk-128", hidden_size=512, n_layers=2, n_heads=4,
+        n_kv_heads=1, head_dim=128, intermediate_size=1024, vocab_size=512,
+        max_position=2048, qk_norm=True),
 }
 
 
@@ -250,6 +283,11 @@ class LlamaForCausalLM:
             self.params[f"l{i}.ln1"] = torch.ones(c.hidden_size, dtype=self.dtype,
                                                   device=self.device)
             self.params[f"l{i}.ln2"] = torch.ones_like(self.params[f"l{i}.ln1"])
+            if c.qk_norm:      # [head_dim]: replicated, not sharded, under TP
+                self.params[f"l{i}.q_norm"] = torch.ones(
+                    c.head_dim, dtype=self.dtype, device=self.device)
+                self.params[f"l{i}.k_norm"] = torch.ones_like(
+                    self.params[f"l{i}.q_norm"])
         gen.manual_seed(seed + 2)
         self.params["final_ln"] = torch.ones(c.hidden_size, dtype=self.dtype,
                                              device=self.device)
@@ -444,6 +482,7 @@ class LlamaForCausalLM:
                 + ("AWQ checkpoints load under quant='int4-awq' only"
                    if is_awq else "quant='int4-awq' loads AWQ checkpoints "
                    "only (nothing is quantized at load)"))
+        self._check_qk_norm_keys(raw, path)
         if is_awq:
             return self._load_awq(raw, path)
 
@@ -476,6 +515,9 @@ class LlamaForCausalLM:
                                              cols=self.inter)
             self.params[f"l{i}.ln1"] = take(p + "input_layernorm.weight")
             self.params[f"l{i}.ln2"] = take(p + "post_attention_layernorm.weight")
+            if c.qk_norm:
+                self.params[f"l{i}.q_norm"] = take(p + "self_attn.q_norm.weight")
+                self.params[f"l{i}.k_norm"] = take(p + "self_attn.k_norm.weight")
         self.params["final_ln"] = take("model.norm.weight")
         if "lm_head.weight" in raw:
             self.params["lm_head"] = take("lm_head.weight")
@@ -486,6 +528,31 @@ class LlamaForCausalLM:
         elif self.quant == "int4":
             self._quantize_weights_int4()
         return loaded
+
+    def _check_qk_norm_keys(self, raw: dict, path: str) -> None:
+        """The checkpoint holds ``self_attn.{q,k}_norm.weight`` for every
+        layer exactly when the model has a q/k norm: a key the model would
+        drop, or one it would miss, names itself here."""
+        c = self.config
+        want = [f"model.layers.{i}.self_attn.{n}_norm.weight"
+                for i in range(c.n_layers) for n in "qk"]
+        if c.qk_norm:
+            for key in want:
+                if key not in raw:
+                    raise ValueError(
+                        f"{path} has no {key}: {c.name} has a q/k norm "
+                        f"(qk_norm=True) and the checkpoint does not")
+                if tuple(raw[key].shape) != (c.head_dim,):
+                    raise ValueError(
+                        f"{path}: {key} has shape {tuple(raw[key].shape)}, "
+                        f"the model [{c.head_dim}]")
+            return
+        for key in sorted(raw):
+            if key.endswith(("self_attn.q_norm.weight",
+                             "self_attn.k_norm.weight")):
+                raise ValueError(
+                    f"{path} holds {key} but {c.name} has no q/k norm "
+                    f"(qk_norm=False): the weight would be dropped")
 
     _AWQ_CONFIG = {"quant_method": "awq", "bits": 4, "group_size": 128,
                    "version": "gemm", "zero_point": True}
@@ -562,6 +629,11 @@ class LlamaForCausalLM:
             self.params[f"l{i}.ln1"] = dense(p + "input_layernorm.weight")
             self.params[f"l{i}.ln2"] = dense(
                 p + "post_attention_layernorm.weight")
+            if c.qk_norm:
+                self.params[f"l{i}.q_norm"] = dense(
+                    p + "self_attn.q_norm.weight")
+                self.params[f"l{i}.k_norm"] = dense(
+                    p + "self_attn.k_norm.weight")
         self.params["final_ln"] = dense("model.norm.weight")
         self.params["lm_head"] = dense("lm_head.weight") \
             if "lm_head.weight" in raw else self.params["embed"]
@@ -594,6 +666,9 @@ class LlamaForCausalLM:
             out[p + "mlp.down_proj.weight"] = self.params[f"l{i}.down"]
             out[p + "input_layernorm.weight"] = self.params[f"l{i}.ln1"]
             out[p + "post_attention_layernorm.weight"] = self.params[f"l{i}.ln2"]
+            if c.qk_norm:
+                out[p + "self_attn.q_norm.weight"] = self.params[f"l{i}.q_norm"]
+                out[p + "self_attn.k_norm.weight"] = self.params[f"l{i}.k_norm"]
         out["model.norm.weight"] = self.params["final_ln"]
         if self.params["lm_head"] is not self.params["embed"]:
             out["lm_head.weight"] = self.params["lm_head"]
@@ -850,6 +925,21 @@ class LlamaForCausalLM:
             adapter_idx))
         return mlp, residual
 
+    def _rope_kv_append(self, i: int, qkv: torch.Tensor,
+                        positions: torch.Tensor, k_cache: torch.Tensor,
+                        v_cache: torch.Tensor,
+                        slot_mapping: torch.Tensor) -> None:
+        """RoPE + cache append on layer i's raw qkv rows, after the q/k norm
+        where the model has one (one kernel either way)."""
+        if self.config.qk_norm:
+            ops.qk_norm_rope_kv_append_qkv_(
+                qkv, self.params[f"l{i}.q_norm"], self.params[f"l{i}.k_norm"],
+                self.config.rms_eps, positions, self.cos_sin, k_cache,
+                v_cache, slot_mapping, self.n_heads)
+        else:
+            ops.rope_kv_append_qkv_(qkv, positions, self.cos_sin, k_cache,
+                                    v_cache, slot_mapping, self.n_heads)
+
     def forward_prefill(self, input_ids: torch.Tensor, positions: torch.Tensor,
                         kv_cache, slot_mapping: torch.Tensor,
                         cu_seqlens: torch.Tensor,
@@ -858,8 +948,8 @@ class LlamaForCausalLM:
         """Returns logits for the LAST token of each sequence:
         [n_seqs, vocab]."""
         def attn(i, qkv, k_cache, v_cache):
-            ops.rope_kv_append_qkv_(qkv, positions, self.cos_sin, k_cache,
-                                    v_cache, slot_mapping, self.n_heads)
+            self._rope_kv_append(i, qkv, positions, k_cache, v_cache,
+                                 slot_mapping)
             return ops.prefill_attn_qkv(qkv, cu_seqlens, self.scale,
                                         self.n_heads, self.n_kv_heads,
                                         self.config.head_dim)
@@ -884,8 +974,8 @@ class LlamaForCausalLM:
         are prefill-chunk tokens attending over the paged cache
         (chunked prefill).  Returns logits for ``sample_idx`` rows."""
         def attn(i, qkv, k_cache, v_cache):
-            ops.rope_kv_append_qkv_(qkv, positions, self.cos_sin, k_cache,
-                                    v_cache, slot_mapping, self.n_heads)
+            self._rope_kv_append(i, qkv, positions, k_cache, v_cache,
+                                 slot_mapping)
             out = ops.prefill_paged_attn(
                 qkv, k_cache, v_cache, chunk_row0, chunk_pos0, chunk_nrows,
                 chunk_btrow, block_tables_pre, self.scale, self.n_heads)
@@ -912,11 +1002,17 @@ class LlamaForCausalLM:
         serves every layer."""
         def attn(i, qkv, k_cache, v_cache):
             if shared_plan is not None:
-                ops.rope_kv_append_qkv_(qkv, positions, self.cos_sin, k_cache,
-                                        v_cache, slot_mapping, self.n_heads)
+                self._rope_kv_append(i, qkv, positions, k_cache, v_cache,
+                                     slot_mapping)
                 return ops.decode_attn_shared_qkv(
                     qkv, k_cache, v_cache, block_tables, seq_lens,
                     shared_plan, self.scale, self.n_heads)
+            if self.config.qk_norm:
+                return ops.decode_attn_qknorm_rope_qkv(
+                    qkv, self.params[f"l{i}.q_norm"],
+                    self.params[f"l{i}.k_norm"], self.config.rms_eps,
+                    positions, self.cos_sin, k_cache, v_cache, slot_mapping,
+                    block_tables, seq_lens, self.scale, self.n_heads)
             return ops.decode_attn_rope_qkv(
                 qkv, positions, self.cos_sin, k_cache, v_cache, slot_mapping,
                 block_tables, seq_lens, self.scale, self.n_heads)

@@ -157,6 +157,52 @@ def decode_attn_rope_qkv(qkv, positions, cos_sin, k_cache, v_cache,
                            scale, n_q)
 
 
+def qk_norm_rope_kv_append_qkv_(qkv: torch.Tensor, q_norm_w: torch.Tensor,
+                                k_norm_w: torch.Tensor, eps: float,
+                                positions: torch.Tensor,
+                                cos_sin: torch.Tensor, k_cache: torch.Tensor,
+                                v_cache: torch.Tensor,
+                                slot_mapping: torch.Tensor, n_q: int) -> None:
+    """``rope_kv_append_qkv_`` for models with a q/k norm (Qwen3): every q
+    head and k head of the raw qkv rows goes through RMSNorm over its
+    head_dim values (``q_norm_w`` / ``k_norm_w``, [head_dim], shared by all
+    heads; the normalised value stays in f32) and is then rotated, rounded
+    to bf16 and appended as there.
+    v is untouched.  One kernel; head_dim 64 or 128."""
+    if qkv.is_cuda:
+        _gpu()
+        torch.ops.rlli.qk_norm_rope_kv_append_qkv_(
+            qkv, q_norm_w, k_norm_w, eps, positions, cos_sin, k_cache,
+            v_cache, slot_mapping, n_q)
+        return
+    T = qkv.shape[0]
+    n_kv, D = k_cache.shape[1], k_cache.shape[3]
+    q = qkv[:, :n_q * D].view(T, n_q, D)
+    k = qkv[:, n_q * D:(n_q + n_kv) * D].view(T, n_kv, D)
+    v = qkv[:, (n_q + n_kv) * D:].view(T, n_kv, D)
+    ref.qk_norm_rope_kv_append_(q, k, v, q_norm_w, k_norm_w, eps, positions,
+                                cos_sin, k_cache, v_cache, slot_mapping)
+
+
+def decode_attn_qknorm_rope_qkv(qkv, q_norm_w, k_norm_w, eps: float,
+                                positions, cos_sin, k_cache, v_cache,
+                                slot_mapping, block_table, seq_lens,
+                                scale: float, n_q: int) -> torch.Tensor:
+    """``decode_attn_rope_qkv`` with the q/k norm of
+    ``qk_norm_rope_kv_append_qkv_`` applied in registers before the
+    rotation: still one kernel on GPU (cache block size 16 only, the
+    engine's); composed from the unfused ops on CPU."""
+    if qkv.is_cuda:
+        _gpu()
+        return torch.ops.rlli.decode_attn_qknorm_rope_qkv(
+            qkv, q_norm_w, k_norm_w, eps, positions, cos_sin, k_cache,
+            v_cache, slot_mapping, block_table, seq_lens, scale, n_q)
+    qk_norm_rope_kv_append_qkv_(qkv, q_norm_w, k_norm_w, eps, positions,
+                                cos_sin, k_cache, v_cache, slot_mapping, n_q)
+    return decode_attn_qkv(qkv, k_cache, v_cache, block_table, seq_lens,
+                           scale, n_q)
+
+
 def shared_prefix_chunks(tiles: int, n_kv: int, kv_tiles: int) -> int:
     """Chunks of the shared prefix per (row tile, kv-head) that fill the
     device: what a ``decode_attn_shared_qkv`` plan's workspace is sized

@@ -36,6 +36,7 @@ SOURCES = [
     "rmsnorm.hip",
     "silu_mul.hip",
     "rope_kv.hip",
+    "qk_norm_rope.hip",
     "decode_attn.hip",
     "decode_attn_shared.hip",
     "prefill_attn.hip",
@@ -64,6 +65,7 @@ HEADERS = ["common.h", "kernels.h", "sampling_common.h", "w4a16_common.h"]
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
     "sampling_nucleus.hip": _NO_PK_F32,
+    "qk_norm_rope.hip": _NO_PK_F32,
     "decode_attn_shared.hip": _NO_PK_F32,
     "w4a16_zp.hip": _NO_PK_F32,
     "w4a16_silu.hip": _NO_PK_F32,

@@ -47,8 +47,22 @@ constexpr float kNegInf = -1e30f;
 // WRONG, never used for real inference): 1 = skip LDS publish/merge,
 // 2 = skip online softmax, 3 = loads only.  Isolates which phase owns
 // the wall time (guide pitfall 8: ablate before optimizing).
+// NORM (FUSED only): an empty pack, or one QkNormArgs for the Qwen3
+// per-head RMSNorm of qk_norm_rope.hip, n = x * rsqrt(mean(x^2) + eps) * w
+// in f32, applied in registers to each of the GROUP query heads and to the
+// new k between the load and the rotation: one more group_sum_dpp<GW> per
+// head.  Every split workgroup recomputes the q norms (cheap, and no
+// cross-workgroup dependency).  The norm's arguments are a trailing pack
+// so that without them the kernel's argument list, and with it its code,
+// is what it was before the norm existed.
+struct QkNormArgs {
+  const uint16_t* q_w;     // [D] bf16
+  const uint16_t* k_w;
+  float eps;
+};
+
 template <int GW, int GROUP, bool FUSED, int BS = 0, int ABL = 0,
-          typename KC = CacheBF16>
+          typename KC = CacheBF16, typename... NORM>
 __global__ __launch_bounds__(256)
 void decode_attn_kernel(const uint16_t* __restrict__ q,
                         const typename KC::elem* __restrict__ k_cache,
@@ -67,7 +81,11 @@ void decode_attn_kernel(const uint16_t* __restrict__ q,
                         typename KC::elem* __restrict__ v_cache_w,
                         int n_split,
                         float* __restrict__ part_out,
-                        float* __restrict__ part_ml) {
+                        float* __restrict__ part_ml,
+                        NORM... norm) {
+  constexpr bool QKN = sizeof...(NORM) == 1;
+  static_assert(sizeof...(NORM) <= 1 && (FUSED || !QKN),
+                "the q/k norm lives in the fused path");
   constexpr int D = GW * 8;
   constexpr int GPW = 64 / GW;                 // lane-groups per wave
   const int block_size = BS ? BS : block_size_rt;
@@ -119,6 +137,22 @@ void decode_attn_kernel(const uint16_t* __restrict__ q,
       cs_c[i] = cs[pidx + i];
       cs_s[i] = cs[HALF + pidx + i];
     }
+    if constexpr (QKN) {
+      // normalise every query head: the lane-group holds the whole head
+      const QkNormArgs na{norm...};
+      bf16x8 wq;
+      wq.u = *reinterpret_cast<const uint4*>(na.q_w + d0);
+#pragma unroll
+      for (int h = 0; h < GROUP; ++h) {
+        float ss = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) ss += qv[h][i] * qv[h][i];
+        const float inv = rsqrtf(group_sum_dpp<GW>(ss) / D + na.eps);
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+          qv[h][i] = qv[h][i] * inv * bf16_to_f32(wq.s[i]);
+      }
+    }
     // rotate every query head in place
 #pragma unroll
     for (int h = 0; h < GROUP; ++h) {
@@ -151,13 +185,37 @@ void decode_attn_kernel(const uint16_t* __restrict__ q,
       vr.u = *reinterpret_cast<const uint4*>(
           v_src + int64_t(seq) * q_stride + kvh * D + d0);
       float kf[8], vf[8];
+      if constexpr (QKN) {
+        // normalise the new k in f32, as q, then rotate it.  A branch of
+        // its own: routing the plain path's loop below through a shared
+        // f32 array moved the code of the kernels without the norm.
+        const QkNormArgs na{norm...};
+        bf16x8 wk;
+        wk.u = *reinterpret_cast<const uint4*>(na.k_w + d0);
+        float kn[8], ss = 0.f;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float own = bf16_to_f32(kr.s[i]);
-        const float other = __shfl_xor(own, GW / 2, kWave);
-        kf[i] = first_half ? own * cs_c[i] - other * cs_s[i]
-                           : own * cs_c[i] + other * cs_s[i];
-        vf[i] = bf16_to_f32(vr.s[i]);
+        for (int i = 0; i < 8; ++i) {
+          kn[i] = bf16_to_f32(kr.s[i]);
+          ss += kn[i] * kn[i];
+        }
+        const float inv = rsqrtf(group_sum_dpp<GW>(ss) / D + na.eps);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const float own = kn[i] * inv * bf16_to_f32(wk.s[i]);
+          const float other = __shfl_xor(own, GW / 2, kWave);
+          kf[i] = first_half ? own * cs_c[i] - other * cs_s[i]
+                             : own * cs_c[i] + other * cs_s[i];
+          vf[i] = bf16_to_f32(vr.s[i]);
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const float own = bf16_to_f32(kr.s[i]);
+          const float other = __shfl_xor(own, GW / 2, kWave);
+          kf[i] = first_half ? own * cs_c[i] - other * cs_s[i]
+                             : own * cs_c[i] + other * cs_s[i];
+          vf[i] = bf16_to_f32(vr.s[i]);
+        }
       }
       const int32_t slot = slot_mapping[seq];
       const int64_t cbase =
@@ -512,6 +570,7 @@ struct FusedArgs {
   const int32_t* slot_mapping = nullptr;
   void* k_cache_w = nullptr;     // cache-codec elem type
   void* v_cache_w = nullptr;
+  QkNormArgs norm = {nullptr, nullptr, 0.f};   // q_w set: the q/k-norm kernel
 };
 
 template <int GW, int GROUP, typename KC>
@@ -532,7 +591,24 @@ void dispatch_decode(const uint16_t* q, const void* k_cache_v,
   auto launch = [&](auto bs_tag, auto abl_tag) {
     constexpr int BS = decltype(bs_tag)::value;
     constexpr int ABL = decltype(abl_tag)::value;
-    if (fa != nullptr) {
+    if (fa != nullptr && fa->norm.q_w != nullptr) {
+      // the q/k-norm kernel: no ablation forms, and block size 16 only
+      // (the caller validates) - the runtime-block-size form at head_dim
+      // 64, GROUP 8, fp8 cache did not fit the register file without
+      // spills
+      if constexpr (BS == 16) {
+        hipLaunchKernelGGL((decode_attn_kernel<GW, GROUP, true, BS, 0, KC,
+                                               QkNormArgs>),
+                           grid, dim3(256), smem, stream,
+                           q, k_cache, v_cache, block_table, seq_lens, out,
+                           n_kv_heads, block_size, max_blocks, scale, q_stride,
+                           fa->k_src, fa->v_src, fa->positions, fa->cos_sin,
+                           fa->slot_mapping,
+                           static_cast<CElem*>(fa->k_cache_w),
+                           static_cast<CElem*>(fa->v_cache_w),
+                           n_split, part_out, part_ml, fa->norm);
+      }
+    } else if (fa != nullptr) {
       hipLaunchKernelGGL((decode_attn_kernel<GW, GROUP, true, BS, ABL, KC>),
                          grid, dim3(256), smem, stream,
                          q, k_cache, v_cache, block_table, seq_lens, out,
@@ -674,6 +750,30 @@ void launch_decode_attn_fused(
   fa.slot_mapping = slot_mapping;
   fa.k_cache_w = k_cache;
   fa.v_cache_w = v_cache;
+  launch_decode_attn_impl(qkv, k_cache, v_cache, block_table, seq_lens, out,
+                          batch, n_q_heads, n_kv_heads, head_dim, block_size,
+                          max_blocks, scale, qkv_stride, &fa,
+                          n_split, part_out, part_ml, cache_fp8, stream);
+}
+
+void launch_decode_attn_fused_qknorm(
+    const uint16_t* qkv, const uint16_t* q_norm_w, const uint16_t* k_norm_w,
+    float eps, void* k_cache, void* v_cache,
+    const int32_t* block_table, const int32_t* seq_lens,
+    const int32_t* positions, const float* cos_sin,
+    const int32_t* slot_mapping, uint16_t* out, int batch, int n_q_heads,
+    int n_kv_heads, int head_dim, int block_size, int max_blocks,
+    float scale, int qkv_stride, int n_split, float* part_out,
+    float* part_ml, bool cache_fp8, hipStream_t stream) {
+  FusedArgs fa;
+  fa.k_src = qkv + n_q_heads * head_dim;
+  fa.v_src = qkv + (n_q_heads + n_kv_heads) * head_dim;
+  fa.positions = positions;
+  fa.cos_sin = cos_sin;
+  fa.slot_mapping = slot_mapping;
+  fa.k_cache_w = k_cache;
+  fa.v_cache_w = v_cache;
+  fa.norm = {q_norm_w, k_norm_w, eps};
   launch_decode_attn_impl(qkv, k_cache, v_cache, block_table, seq_lens, out,
                           batch, n_q_heads, n_kv_heads, head_dim, block_size,
                           max_blocks, scale, qkv_stride, &fa,

@@ -228,6 +228,52 @@ void rope_kv_append_qkv_(Tensor qkv, const Tensor& positions,
   check_launch("rope_kv_append_qkv_");
 }
 
+// q/k norm weights (Qwen3): [head_dim] bf16 on the data's device
+void check_qk_norm_w(const Tensor& w, const Tensor& qkv, int D,
+                     const char* name) {
+  TORCH_CHECK(w.scalar_type() == at::kBFloat16 && w.is_contiguous() &&
+              w.device() == qkv.device() && w.dim() == 1 && w.size(0) == D,
+              name, " must be a contiguous bf16 [", D, "] tensor on the "
+              "data's device");
+}
+
+// rope_kv_append_qkv_ with the per-head RMSNorm of q and k before the
+// rotation (qk_norm_rope.hip).
+void qk_norm_rope_kv_append_qkv_(Tensor qkv, const Tensor& q_norm_w,
+                                 const Tensor& k_norm_w, double eps,
+                                 const Tensor& positions,
+                                 const Tensor& cos_sin, Tensor k_cache,
+                                 Tensor v_cache, const Tensor& slot_mapping,
+                                 int64_t n_q) {
+  check_bf16_contig(qkv, "qkv");
+  const bool cache_fp8 = check_cache(k_cache, v_cache);
+  TORCH_CHECK(positions.scalar_type() == at::kInt && positions.is_contiguous());
+  TORCH_CHECK(slot_mapping.scalar_type() == at::kInt && slot_mapping.is_contiguous());
+  TORCH_CHECK(cos_sin.scalar_type() == at::kFloat && cos_sin.is_contiguous());
+  const int n_kv = int(k_cache.size(1));
+  const int D = int(k_cache.size(3));
+  const int block_size = int(k_cache.size(2));
+  const int stride = int(qkv.size(1));
+  TORCH_CHECK(n_q >= 1 && stride == (n_q + 2 * n_kv) * D, "qkv width mismatch");
+  TORCH_CHECK(D == 64 || D == 128, "head_dim must be 64 or 128, got ", D);
+  check_qk_norm_w(q_norm_w, qkv, D, "q_norm_w");
+  check_qk_norm_w(k_norm_w, qkv, D, "k_norm_w");
+  const int tokens = int(qkv.size(0));
+  TORCH_CHECK(positions.numel() == tokens && slot_mapping.numel() == tokens);
+  TORCH_CHECK(cos_sin.size(1) == D && v_cache.sizes() == k_cache.sizes());
+  uint16_t* base = bf16_ptr(qkv);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(qkv.device());
+  rlli::launch_qk_norm_rope_kv_append(
+      base, base + n_q * D, base + (n_q + n_kv) * D,
+      bf16_ptr(q_norm_w), bf16_ptr(k_norm_w), float(eps),
+      positions.data_ptr<int32_t>(), cos_sin.data_ptr<float>(),
+      k_cache.data_ptr(), v_cache.data_ptr(),
+      slot_mapping.data_ptr<int32_t>(),
+      tokens, int(n_q), n_kv, D, block_size, stride, stride, cache_fp8,
+      current_stream(qkv));
+  check_launch("qk_norm_rope_kv_append_qkv_");
+}
+
 
 // split-K scratch for decode attention (empty tensors when n_split==1);
 // allocation participates in hipGraph capture pools, so graphed decode
@@ -364,6 +410,58 @@ Tensor decode_attn_rope_qkv(const Tensor& qkv, const Tensor& positions,
       ss.n_split, ss.part_ptr(), ss.ml_ptr(), cache_fp8,
       current_stream(qkv));
   check_launch("decode_attn_rope_qkv");
+  return out;
+}
+
+// decode_attn_rope_qkv with the q/k norm in registers before the rotation.
+Tensor decode_attn_qknorm_rope_qkv(const Tensor& qkv, const Tensor& q_norm_w,
+                                   const Tensor& k_norm_w, double eps,
+                                   const Tensor& positions,
+                                   const Tensor& cos_sin, Tensor k_cache,
+                                   Tensor v_cache, const Tensor& slot_mapping,
+                                   const Tensor& block_table,
+                                   const Tensor& seq_lens, double scale,
+                                   int64_t n_q) {
+  check_bf16_contig(qkv, "qkv");
+  const bool cache_fp8 = check_cache(k_cache, v_cache);
+  TORCH_CHECK(positions.scalar_type() == at::kInt && positions.is_contiguous());
+  TORCH_CHECK(slot_mapping.scalar_type() == at::kInt && slot_mapping.is_contiguous());
+  TORCH_CHECK(cos_sin.scalar_type() == at::kFloat && cos_sin.is_contiguous());
+  TORCH_CHECK(block_table.scalar_type() == at::kInt && block_table.is_contiguous());
+  TORCH_CHECK(seq_lens.scalar_type() == at::kInt && seq_lens.is_contiguous());
+  const int batch = int(qkv.size(0));
+  const int n_kv = int(k_cache.size(1));
+  const int block_size = int(k_cache.size(2));
+  const int D = int(k_cache.size(3));
+  const int stride = int(qkv.size(1));
+  TORCH_CHECK(n_q >= 1 && stride == (n_q + 2 * n_kv) * D, "qkv width mismatch");
+  const int group = int(n_q) / n_kv;
+  TORCH_CHECK(n_q % n_kv == 0 &&
+              (group == 1 || group == 2 || group == 4 || group == 8),
+              "GQA group must be 1/2/4/8, got ", group);
+  TORCH_CHECK(D == 64 || D == 128, "head_dim must be 64 or 128, got ", D);
+  TORCH_CHECK(block_size == 16, "decode_attn_qknorm_rope_qkv: block_size "
+              "must be 16, got ", block_size);
+  check_qk_norm_w(q_norm_w, qkv, D, "q_norm_w");
+  check_qk_norm_w(k_norm_w, qkv, D, "k_norm_w");
+  TORCH_CHECK(cos_sin.size(1) == D && v_cache.sizes() == k_cache.sizes());
+  TORCH_CHECK(positions.numel() == batch && slot_mapping.numel() == batch &&
+              block_table.dim() == 2 && block_table.size(0) == batch &&
+              seq_lens.numel() == batch, "batch mismatch");
+  const int max_blocks = int(block_table.size(1));
+  Tensor out = at::empty({batch, n_q * D}, qkv.options());
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(qkv.device());
+  SplitScratch ss = make_split_scratch(qkv, batch, n_kv, group, D);
+  rlli::launch_decode_attn_fused_qknorm(
+      bf16_ptr(qkv), bf16_ptr(q_norm_w), bf16_ptr(k_norm_w), float(eps),
+      k_cache.data_ptr(), v_cache.data_ptr(),
+      block_table.data_ptr<int32_t>(), seq_lens.data_ptr<int32_t>(),
+      positions.data_ptr<int32_t>(), cos_sin.data_ptr<float>(),
+      slot_mapping.data_ptr<int32_t>(), bf16_ptr(out), batch, int(n_q),
+      n_kv, D, block_size, max_blocks, float(scale), stride,
+      ss.n_split, ss.part_ptr(), ss.ml_ptr(), cache_fp8,
+      current_stream(qkv));
+  check_launch("decode_attn_qknorm_rope_qkv");
   return out;
 }
 
@@ -1347,6 +1445,14 @@ TORCH_LIBRARY(rlli, m) {
   m.def("decode_attn_rope_qkv(Tensor qkv, Tensor positions, Tensor cos_sin, "
         "Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor slot_mapping, "
         "Tensor block_table, Tensor seq_lens, float scale, int n_q) -> Tensor");
+  m.def("qk_norm_rope_kv_append_qkv_(Tensor(a!) qkv, Tensor q_norm_w, "
+        "Tensor k_norm_w, float eps, Tensor positions, Tensor cos_sin, "
+        "Tensor(b!) k_cache, Tensor(c!) v_cache, Tensor slot_mapping, "
+        "int n_q) -> ()");
+  m.def("decode_attn_qknorm_rope_qkv(Tensor qkv, Tensor q_norm_w, "
+        "Tensor k_norm_w, float eps, Tensor positions, Tensor cos_sin, "
+        "Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor slot_mapping, "
+        "Tensor block_table, Tensor seq_lens, float scale, int n_q) -> Tensor");
   m.def("prefill_attn_qkv(Tensor qkv, Tensor cu_seqlens, float scale, "
         "int n_q, int n_kv, int head_dim) -> Tensor");
   m.def("prefill_attn(Tensor q, Tensor k, Tensor v, Tensor cu_seqlens, "
@@ -1416,6 +1522,8 @@ TORCH_LIBRARY_IMPL(rlli, CUDA, m) {
   m.impl("rope_kv_append_qkv_", &rope_kv_append_qkv_);
   m.impl("decode_attn_qkv", &decode_attn_qkv);
   m.impl("decode_attn_rope_qkv", &decode_attn_rope_qkv);
+  m.impl("qk_norm_rope_kv_append_qkv_", &qk_norm_rope_kv_append_qkv_);
+  m.impl("decode_attn_qknorm_rope_qkv", &decode_attn_qknorm_rope_qkv);
   m.impl("decode_attn_shared_qkv", &decode_attn_shared_qkv);
   m.impl("prefill_attn_qkv", &prefill_attn_qkv);
   m.impl("prefill_attn", &prefill_attn);

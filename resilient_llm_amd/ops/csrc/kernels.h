@@ -43,6 +43,21 @@ void launch_rope_kv_append(
     int block_size, int q_stride, int kv_stride, bool cache_fp8,
     hipStream_t stream);
 
+// launch_rope_kv_append with a per-head RMSNorm on q and on k between the
+// projection and the rotation (Qwen3): n = x * rsqrt(mean(x^2) + eps) * w
+// in f32, w = q_norm_w / k_norm_w [head_dim] shared by all heads, then n is
+// rotated, rounded and appended as above; v is untouched.  head_dim 64 or
+// 128.
+void launch_qk_norm_rope_kv_append(
+    uint16_t* q, uint16_t* k, uint16_t* v,
+    const uint16_t* q_norm_w, const uint16_t* k_norm_w, float eps,
+    const int32_t* positions, const float* cos_sin,
+    void* k_cache, void* v_cache,
+    const int32_t* slot_mapping,
+    int tokens, int n_q_heads, int n_kv_heads, int head_dim,
+    int block_size, int q_stride, int kv_stride, bool cache_fp8,
+    hipStream_t stream);
+
 // Split-K factor for decode attention (flash-decode): >1 when
 // batch*n_kv_heads workgroups cannot fill 256 CUs.  The caller sizes
 // the f32 scratch as [batch*n_kv*n_split*group*head_dim] (part_out)
@@ -71,6 +86,19 @@ void launch_decode_attn(
 // kernel (decode path; qkv is the raw fused GEMM output).
 void launch_decode_attn_fused(
     const uint16_t* qkv, void* k_cache, void* v_cache,
+    const int32_t* block_table, const int32_t* seq_lens,
+    const int32_t* positions, const float* cos_sin,
+    const int32_t* slot_mapping, uint16_t* out, int batch, int n_q_heads,
+    int n_kv_heads, int head_dim, int block_size, int max_blocks,
+    float scale, int qkv_stride, int n_split, float* part_out,
+    float* part_ml, bool cache_fp8, hipStream_t stream);
+
+// The fused decode kernel with the q/k RMSNorm of
+// launch_qk_norm_rope_kv_append applied in registers before the rotation.
+// block_size must be 16 (other sizes launch nothing: the caller validates).
+void launch_decode_attn_fused_qknorm(
+    const uint16_t* qkv, const uint16_t* q_norm_w, const uint16_t* k_norm_w,
+    float eps, void* k_cache, void* v_cache,
     const int32_t* block_table, const int32_t* seq_lens,
     const int32_t* positions, const float* cos_sin,
     const int32_t* slot_mapping, uint16_t* out, int batch, int n_q_heads,

@@ -76,6 +76,33 @@ def rope_kv_append_(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     v_cache[blocks, :, rows] = v[valid].to(v_cache.dtype)
 
 
+def qk_norm_rope_kv_append_(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                            q_norm_w: torch.Tensor, k_norm_w: torch.Tensor,
+                            eps: float, positions: torch.Tensor,
+                            cos_sin: torch.Tensor, k_cache: torch.Tensor,
+                            v_cache: torch.Tensor,
+                            slot_mapping: torch.Tensor) -> None:
+    """``rope_kv_append_`` with a per-head RMSNorm of q and of k first
+    (Qwen3): n = f32(x) * rsqrt(mean(x^2) + eps) * f32(w) over each head's
+    D values, w [D] shared by all heads.  n stays in fp32 - as in the
+    kernels, which hold it in registers - and is rotated there; the one
+    rounding to the storage dtype is that of the rotated value.  k at that
+    rounding and v are appended.  v is untouched.  q/k/v: [T, H, D]."""
+    def norm(x, w):
+        xf = x.float()
+        return xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) \
+            * w.float()
+    dt = q.dtype
+    q.copy_(_rotate(norm(q, q_norm_w), positions, cos_sin).to(dt))
+    k.copy_(_rotate(norm(k, k_norm_w), positions, cos_sin).to(dt))
+    block_size = k_cache.shape[2]
+    slots = slot_mapping.long()
+    valid = slots >= 0
+    blocks, rows = slots[valid] // block_size, slots[valid] % block_size
+    k_cache[blocks, :, rows] = k[valid].to(k_cache.dtype)
+    v_cache[blocks, :, rows] = v[valid].to(v_cache.dtype)
+
+
 def decode_attn(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
                 block_table: torch.Tensor, seq_lens: torch.Tensor,
                 scale: float) -> torch.Tensor:
