@@ -147,6 +147,21 @@ def _require(cond: bool, msg: str) -> None:
         raise ConfigError(msg)
 
 
+# The model presets with num_experts > 0 (models/llama.py MODEL_PRESETS;
+# listed here because this module does not import torch).
+MOE_MODELS = frozenset({"qwen3-30b-a3b", "tiny-moe"})
+
+
+def _worker_adapters(deployments: list, d: "Deployment") -> dict:
+    """The adapters any deployment loads on ``d``'s worker."""
+    out: dict = {}
+    for e in deployments:
+        if (e.backend_kind == d.backend_kind
+                and e.backend_target == d.backend_target):
+            out.update(e.params.get("adapters") or {})
+    return out
+
+
 def _parse_deployment(entry: Any, idx: int) -> Deployment:
     _require(isinstance(entry, dict), f"model_list[{idx}] must be a mapping")
     name = entry.get("model_name")
@@ -355,6 +370,28 @@ def load_config(path: str | os.PathLike[str] | None = None,
                          f"deployment {d.model_name}: adapters are served "
                          f"by gpu/<device> workers only, not by pool "
                          f"{d.backend_target!r}")
+    # Mixture-of-Experts models: bf16 experts on one gpu/ worker.  The
+    # expert kernels read bf16 weights only, the experts do not shard, the
+    # adapter kernels know the dense MLP only, and pool workers build their
+    # models through the tensor-parallel path.
+    for d in deployments:
+        if d.backend_model not in MOE_MODELS:
+            continue
+        what = f"deployment {d.model_name}: {d.backend_model} is a " \
+               f"Mixture-of-Experts model and "
+        _require(not d.params.get("quantization"),
+                 what + f"cannot be combined with quantization: "
+                 f"{d.params.get('quantization')} (its experts are served in "
+                 f"bf16)")
+        _require("adapter" not in d.params and "adapters" not in d.params
+                 and not _worker_adapters(deployments, d),
+                 what + "cannot be combined with adapters")
+        if d.backend_kind == "pool":
+            tp = cluster.pools[d.backend_target].tensor_parallel
+            _require(tp == 1, what + f"does not shard: pool "
+                     f"{d.backend_target!r} has tensor_parallel {tp} > 1")
+            _require(False, what + f"is served by gpu/<device> workers only, "
+                     f"not by pool {d.backend_target!r}")
     # every fallback target must be a known alias
     known = {d.model_name for d in deployments}
     for alias, targets in router.fallbacks.items():

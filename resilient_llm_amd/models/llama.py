@@ -69,6 +69,14 @@ class LlamaConfig:
     # Qwen3: a per-head RMSNorm on q and on k (weights [head_dim], shared by
     # all heads) between the qkv projection and RoPE
     qk_norm: bool = False
+    # Qwen3-MoE: every layer's MLP is num_experts SwiGLU experts of width
+    # moe_intermediate_size, experts_per_token of them run per token,
+    # weighted by a softmax-top-k router (norm_topk_prob: the chosen
+    # weights are renormalised to sum to 1).  0 experts: the dense MLP.
+    num_experts: int = 0
+    experts_per_token: int = 0
+    moe_intermediate_size: int = 0
+    norm_topk_prob: bool = True
 
     @property
     def q_size(self) -> int:
@@ -121,7 +129,23 @@ MODEL_PRESETS: dict[str, LlamaConfig] = {
         n_kv_heads=8, head_dim=128, intermediate_size=25600,
         vocab_size=151936, rope_theta=1000000.0, rms_eps=1e-6,
         max_position=40960, eos_ids=(151645, 151643), qk_norm=True),
+    # Qwen3-MoE: qwen3-8b's attention side at hidden 2048 and a sparse MLP
+    # in every layer, no shared expert.  As above the geometry is written
+    # from memory of the published config.json, and load_safetensors' shape
+    # checks are what catches a wrong number.
+    "qwen3-30b-a3b": LlamaConfig(
+        name="qwen3-30b-a3b", hidden_size=2048, n_layers=48, n_heads=32,
+        n_kv_heads=4, head_dim=128, intermediate_size=6144,
+        vocab_size=151936, rope_theta=1000000.0, rms_eps=1e-6,
+        max_position=40960, eos_ids=(151645, 151643), qk_norm=True,
+        num_experts=128, experts_per_token=8, moe_intermediate_size=768,
+        norm_topk_prob=True),
     # CPU-testable models
+    "tiny-moe": LlamaConfig(
+        name="tiny-moe", hidden_size=256, n_layers=2, n_heads=4,
+        n_kv_heads=2, head_dim=64, intermediate_size=512, vocab_size=512,
+        max_position=2048, qk_norm=True, num_experts=8,
+        experts_per_token=2, moe_intermediate_size=128),
     "tiny": LlamaConfig(
         name="tiny", hidden_size=256, n_layers=2, n_heads=4, n_kv_heads=2,
         head_dim=64, intermediate_size=512, vocab_size=512,
@@ -204,6 +228,16 @@ class LlamaForCausalLM:
         if quant == "int4-awq" and tp_world > 1:
             raise ValueError("quant='int4-awq' does not shard: "
                              "tensor_parallel must be 1")
+        # Mixture-of-Experts configs (num_experts > 0): bf16 experts on one
+        # GPU, routed by ops.moe_route and run by ops.moe_mlp in every step
+        # (prefill, mixed, decode and the captured graph alike)
+        if config.num_experts:
+            if quant is not None:
+                raise ValueError(f"{config.name} is a Mixture-of-Experts "
+                                 f"model: quant must be None, got {quant!r}")
+            if tp_world > 1:
+                raise ValueError(f"{config.name} is a Mixture-of-Experts "
+                                 f"model: tensor_parallel must be 1")
         self.quant = quant
         self.tp_rank = tp_rank
         self.tp_world = tp_world
@@ -273,13 +307,23 @@ class LlamaForCausalLM:
                 vf[r * self.kv_size:(r + 1) * self.kv_size]], dim=0).contiguous()
             o = self._full((c.hidden_size, c.q_size), gen, std_o)
             self.params[f"l{i}.o"] = o[:, r * self.q_size:(r + 1) * self.q_size].contiguous()
-            gu = self._full((2 * c.intermediate_size, c.hidden_size), gen)
-            gf, uf = torch.split(gu, [c.intermediate_size, c.intermediate_size], dim=0)
-            self.params[f"l{i}.gate_up"] = torch.cat([
-                gf[r * self.inter:(r + 1) * self.inter],
-                uf[r * self.inter:(r + 1) * self.inter]], dim=0).contiguous()
-            down = self._full((c.hidden_size, c.intermediate_size), gen, std_o)
-            self.params[f"l{i}.down"] = down[:, r * self.inter:(r + 1) * self.inter].contiguous()
+            if c.num_experts:
+                E, I = c.num_experts, c.moe_intermediate_size
+                # a wider router than 0.02 so that random weights spread
+                # the tokens over the experts with distinct logits
+                self._mk(f"l{i}.router", (E, c.hidden_size), gen, 0.5)
+                self._mk(f"l{i}.experts_gate_up", (E, 2 * I, c.hidden_size),
+                         gen)
+                self._mk(f"l{i}.experts_down", (E, c.hidden_size, I), gen,
+                         std_o)
+            else:
+                gu = self._full((2 * c.intermediate_size, c.hidden_size), gen)
+                gf, uf = torch.split(gu, [c.intermediate_size, c.intermediate_size], dim=0)
+                self.params[f"l{i}.gate_up"] = torch.cat([
+                    gf[r * self.inter:(r + 1) * self.inter],
+                    uf[r * self.inter:(r + 1) * self.inter]], dim=0).contiguous()
+                down = self._full((c.hidden_size, c.intermediate_size), gen, std_o)
+                self.params[f"l{i}.down"] = down[:, r * self.inter:(r + 1) * self.inter].contiguous()
             self.params[f"l{i}.ln1"] = torch.ones(c.hidden_size, dtype=self.dtype,
                                                   device=self.device)
             self.params[f"l{i}.ln2"] = torch.ones_like(self.params[f"l{i}.ln1"])
@@ -483,6 +527,7 @@ class LlamaForCausalLM:
                    if is_awq else "quant='int4-awq' loads AWQ checkpoints "
                    "only (nothing is quantized at load)"))
         self._check_qk_norm_keys(raw, path)
+        self._check_moe_keys(raw, path)
         if is_awq:
             return self._load_awq(raw, path)
 
@@ -508,11 +553,22 @@ class LlamaForCausalLM:
             self.params[f"l{i}.qkv"] = torch.cat([q, k, v], dim=0).contiguous()
             self.params[f"l{i}.o"] = take(p + "self_attn.o_proj.weight",
                                           cols=self.q_size)
-            g = take(p + "mlp.gate_proj.weight", rows=self.inter)
-            u = take(p + "mlp.up_proj.weight", rows=self.inter)
-            self.params[f"l{i}.gate_up"] = torch.cat([g, u], dim=0).contiguous()
-            self.params[f"l{i}.down"] = take(p + "mlp.down_proj.weight",
-                                             cols=self.inter)
+            if c.num_experts:
+                self.params[f"l{i}.router"] = take(p + "mlp.gate.weight")
+                x = p + "mlp.experts."
+                self.params[f"l{i}.experts_gate_up"] = torch.stack([
+                    torch.cat([take(f"{x}{j}.gate_proj.weight"),
+                               take(f"{x}{j}.up_proj.weight")], dim=0)
+                    for j in range(c.num_experts)]).contiguous()
+                self.params[f"l{i}.experts_down"] = torch.stack([
+                    take(f"{x}{j}.down_proj.weight")
+                    for j in range(c.num_experts)]).contiguous()
+            else:
+                g = take(p + "mlp.gate_proj.weight", rows=self.inter)
+                u = take(p + "mlp.up_proj.weight", rows=self.inter)
+                self.params[f"l{i}.gate_up"] = torch.cat([g, u], dim=0).contiguous()
+                self.params[f"l{i}.down"] = take(p + "mlp.down_proj.weight",
+                                                 cols=self.inter)
             self.params[f"l{i}.ln1"] = take(p + "input_layernorm.weight")
             self.params[f"l{i}.ln2"] = take(p + "post_attention_layernorm.weight")
             if c.qk_norm:
@@ -553,6 +609,45 @@ class LlamaForCausalLM:
                 raise ValueError(
                     f"{path} holds {key} but {c.name} has no q/k norm "
                     f"(qk_norm=False): the weight would be dropped")
+
+    def _check_moe_keys(self, raw: dict, path: str) -> None:
+        """A Mixture-of-Experts model needs the router (``mlp.gate.weight``)
+        and every expert's three projections, at the model's shapes, and no
+        dense ``mlp.{gate,up,down}_proj``; a dense model the reverse.  The
+        first key that is missing, misshapen or would be dropped names
+        itself."""
+        c = self.config
+        E, I, H = c.num_experts, c.moe_intermediate_size, c.hidden_size
+        if not E:
+            for key in sorted(raw):
+                if ".mlp.experts." in key or key.endswith(".mlp.gate.weight"):
+                    raise ValueError(
+                        f"{path} holds {key} but {c.name} has a dense MLP "
+                        f"(num_experts=0): the weight would be dropped")
+            return
+        for i in range(c.n_layers):
+            p = f"model.layers.{i}.mlp."
+            for n in ("gate_proj", "up_proj", "down_proj"):
+                if f"{p}{n}.weight" in raw:
+                    raise ValueError(
+                        f"{path} holds {p}{n}.weight but {c.name} is a "
+                        f"Mixture-of-Experts model (num_experts={E}): the "
+                        f"dense MLP weight would be dropped")
+            want = {p + "gate.weight": (E, H)}
+            for j in range(E):
+                want[f"{p}experts.{j}.gate_proj.weight"] = (I, H)
+                want[f"{p}experts.{j}.up_proj.weight"] = (I, H)
+                want[f"{p}experts.{j}.down_proj.weight"] = (H, I)
+            for key, shape in want.items():
+                if key not in raw:
+                    raise ValueError(
+                        f"{path} has no {key}: {c.name} is a Mixture-of-"
+                        f"Experts model (num_experts={E}) and the checkpoint "
+                        f"does not hold it")
+                if tuple(raw[key].shape) != shape:
+                    raise ValueError(
+                        f"{path}: {key} has shape {tuple(raw[key].shape)}, "
+                        f"the model {list(shape)}")
 
     _AWQ_CONFIG = {"quant_method": "awq", "bits": 4, "group_size": 128,
                    "version": "gemm", "zero_point": True}
@@ -659,11 +754,22 @@ class LlamaForCausalLM:
             out[p + "self_attn.k_proj.weight"] = k
             out[p + "self_attn.v_proj.weight"] = v
             out[p + "self_attn.o_proj.weight"] = self.params[f"l{i}.o"]
-            gu = self.params[f"l{i}.gate_up"]
-            g, u = torch.split(gu, [c.intermediate_size, c.intermediate_size], dim=0)
-            out[p + "mlp.gate_proj.weight"] = g
-            out[p + "mlp.up_proj.weight"] = u
-            out[p + "mlp.down_proj.weight"] = self.params[f"l{i}.down"]
+            if c.num_experts:
+                I = c.moe_intermediate_size
+                out[p + "mlp.gate.weight"] = self.params[f"l{i}.router"]
+                for j in range(c.num_experts):
+                    x = f"{p}mlp.experts.{j}."
+                    gu = self.params[f"l{i}.experts_gate_up"][j]
+                    out[x + "gate_proj.weight"] = gu[:I]
+                    out[x + "up_proj.weight"] = gu[I:]
+                    out[x + "down_proj.weight"] = \
+                        self.params[f"l{i}.experts_down"][j]
+            else:
+                gu = self.params[f"l{i}.gate_up"]
+                g, u = torch.split(gu, [c.intermediate_size, c.intermediate_size], dim=0)
+                out[p + "mlp.gate_proj.weight"] = g
+                out[p + "mlp.up_proj.weight"] = u
+                out[p + "mlp.down_proj.weight"] = self.params[f"l{i}.down"]
             out[p + "input_layernorm.weight"] = self.params[f"l{i}.ln1"]
             out[p + "post_attention_layernorm.weight"] = self.params[f"l{i}.ln2"]
             if c.qk_norm:
@@ -717,6 +823,9 @@ class LlamaForCausalLM:
         if self.quant is not None:
             raise RuntimeError("LoRA adapters are not supported on a "
                                "weight-quantized model")
+        if self.config.num_experts:
+            raise RuntimeError("LoRA adapters are not supported on a "
+                               "Mixture-of-Experts model")
         r = int(r)
         if not 1 <= r <= self.LORA_MAX_RANK:
             raise ValueError(f"adapter {name!r}: r must be in 1.."
@@ -873,6 +982,12 @@ class LlamaForCausalLM:
             mlp = self._all_reduce(self._linear_fp8(dq, ds, f"l{i}.down"))
             return mlp, residual
         h2 = ops.rmsnorm_residual_(h, residual, p[f"l{i}.ln2"], c.rms_eps)
+        if c.num_experts:
+            ids, w = ops.moe_route(_linear(h2, p[f"l{i}.router"]),
+                                   c.experts_per_token, c.norm_topk_prob)
+            mlp = ops.moe_mlp(h2, ids, w, p[f"l{i}.experts_gate_up"],
+                              p[f"l{i}.experts_down"])
+            return mlp, residual
         gu = _linear(h2, p[f"l{i}.gate_up"])
         mlp = self._all_reduce(_linear(ops.silu_mul(gu), p[f"l{i}.down"]))
         return mlp, residual

@@ -777,4 +777,54 @@ def w4a16_wide_plan(N: int, K: int, splitk: int = 0) -> tuple[int, int]:
     return int(sk), int(kps)
 
 
+def moe_route(router_logits: torch.Tensor, k: int, renorm: bool = True
+              ) -> tuple[torch.Tensor, torch.Tensor]:
+    """Softmax-top-k router of a Mixture-of-Experts layer: (ids [T, k]
+    int32, w [T, k] f32) from ``router_logits`` [T, E] bf16.  ids are the k
+    largest logits of the row in descending order, ties to the lower expert
+    index, chosen on the logit values (``ref.moe_route``'s stable sort); w
+    is the f32 softmax over all E at those ids, divided by their sum with
+    ``renorm``.  2 <= E <= 256, 1 <= k <= min(E, 8).  A row holding NaN or
+    Inf still yields k distinct ids in [0, E) (NaN counts as the lowest
+    value); its weights are then not finite."""
+    T, E = router_logits.shape
+    if not 2 <= E <= 256 or not 1 <= k <= min(E, 8):
+        raise ValueError(f"moe_route needs 2 <= E <= 256 and 1 <= k <= "
+                         f"min(E, 8), got E={E} k={k}")
+    if router_logits.is_cuda:
+        _gpu()
+        return torch.ops.rlli.moe_route(router_logits, k, renorm)
+    return ref.moe_route(router_logits, k, renorm)
+
+
+def moe_mlp(x: torch.Tensor, ids: torch.Tensor, w: torch.Tensor,
+            w_gate_up: torch.Tensor, w_down: torch.Tensor,
+            row_tile: int = 0) -> torch.Tensor:
+    """Sparse SwiGLU MLP: out[t] = bf16(sum_j w[t, j] * Wd[e] · bf16(silu(
+    Wg[e] · x[t]) * (Wu[e] · x[t]))) with e = ids[t, j], summed in slot
+    order.  x [T, H] bf16, ids / w [T, k] from ``moe_route``, w_gate_up
+    [E, 2I, H] (gate | up rows), w_down [E, H, I]; H % 64 == 0 and
+    I % 64 == 0.  On the GPU: an alignment kernel sorts the (token, slot)
+    pairs by expert into row tiles of 16 or 64 rows (``row_tile`` = 0
+    picks from T, k and E), a grouped GEMM computes gate and up with SwiGLU
+    in its epilogue, a second one the down projection in f32, and a
+    combine kernel the weighted sum.  Nothing is read back to the host, so
+    the op captures into a graph; no float atomics, so two calls agree bit
+    for bit.  Only the experts some row chose are read, and an id outside
+    [0, E) contributes nothing.  The workspaces are allocated inside."""
+    H, I = x.shape[1], w_down.shape[2]
+    if H % 64 or I % 64:
+        raise ValueError(f"moe_mlp needs H % 64 == 0 and I % 64 == 0, got "
+                         f"H={H} I={I}")
+    if (w_gate_up.shape[1:] != (2 * I, H) or w_down.shape[1] != H
+            or w_down.shape[0] != w_gate_up.shape[0]
+            or ids.shape[0] != x.shape[0] or w.shape != ids.shape):
+        raise ValueError("moe_mlp: x [T, H], ids / w [T, k], w_gate_up "
+                         "[E, 2I, H], w_down [E, H, I] do not fit")
+    if x.is_cuda:
+        _gpu()
+        return torch.ops.rlli.moe_mlp(x, ids, w, w_gate_up, w_down, row_tile)
+    return ref.moe_mlp(x, ids, w, w_gate_up, w_down)
+
+
 build_cos_sin = ref.build_cos_sin

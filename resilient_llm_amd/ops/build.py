@@ -53,6 +53,7 @@ SOURCES = [
     "w4a16_silu.hip",
     "w4a16_tiled.hip",
     "w4a16_wide.hip",
+    "moe.hip",
     "streamprobe.hip",
 ]
 HEADERS = ["common.h", "kernels.h", "sampling_common.h", "w4a16_common.h"]
@@ -71,6 +72,7 @@ EXTRA_FLAGS = {
     "w4a16_silu.hip": _NO_PK_F32,
     "w4a16_tiled.hip": _NO_PK_F32,
     "w4a16_wide.hip": _NO_PK_F32,
+    "moe.hip": _NO_PK_F32,
 }
 
 

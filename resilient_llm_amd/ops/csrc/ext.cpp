@@ -1417,6 +1417,84 @@ void lora_expand_add_(Tensor out, const Tensor& y, const Tensor& B,
   check_launch("lora_expand_add_");
 }
 
+// ------------------------------------------------------------------ moe
+std::tuple<Tensor, Tensor> moe_route(const Tensor& logits, int64_t k,
+                                     bool renorm) {
+  check_bf16_contig(logits, "router_logits");
+  TORCH_CHECK(logits.dim() == 2, "router_logits must be [T, E]");
+  const int64_t T = logits.size(0), E = logits.size(1);
+  TORCH_CHECK(E >= 2 && E <= 256, "moe_route needs 2 <= E <= 256, got ", E);
+  TORCH_CHECK(k >= 1 && k <= std::min<int64_t>(E, 8),
+              "moe_route needs 1 <= k <= min(E, 8), got ", k);
+  TORCH_CHECK(T * k <= INT32_MAX, "moe_route: too many rows");
+  Tensor ids = at::empty({T, k}, logits.options().dtype(at::kInt));
+  Tensor w = at::empty({T, k}, logits.options().dtype(at::kFloat));
+  if (T == 0) return {ids, w};
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(logits.device());
+  rlli::launch_moe_route(bf16_ptr(logits), ids.data_ptr<int32_t>(),
+                         w.data_ptr<float>(), int(T), int(E), int(k), renorm,
+                         current_stream(logits));
+  check_launch("moe_route");
+  return {ids, w};
+}
+
+// row_tile: 0 = moe_row_tile's choice, else 16 or 64 (tuning and tests)
+Tensor moe_mlp(const Tensor& x, const Tensor& ids, const Tensor& w,
+               const Tensor& w_gate_up, const Tensor& w_down,
+               int64_t row_tile) {
+  check_bf16_contig(x, "x");
+  check_bf16_contig(w_gate_up, "w_gate_up");
+  check_bf16_contig(w_down, "w_down");
+  TORCH_CHECK(x.dim() == 2 && w_gate_up.dim() == 3 && w_down.dim() == 3,
+              "moe_mlp: x [T, H], w_gate_up [E, 2I, H], w_down [E, H, I]");
+  const int64_t T = x.size(0), H = x.size(1);
+  const int64_t E = w_gate_up.size(0), I = w_down.size(2);
+  TORCH_CHECK(w_gate_up.size(1) == 2 * I && w_gate_up.size(2) == H &&
+              w_down.size(0) == E && w_down.size(1) == H,
+              "moe_mlp: w_gate_up [E, 2I, H] / w_down [E, H, I] mismatch");
+  TORCH_CHECK(H % 64 == 0 && I % 64 == 0,
+              "moe_mlp needs H % 64 == 0 and I % 64 == 0, got H=", H,
+              " I=", I);
+  TORCH_CHECK(E >= 1 && E <= 256, "moe_mlp needs 1 <= E <= 256, got ", E);
+  TORCH_CHECK(ids.scalar_type() == at::kInt && ids.is_contiguous() &&
+              ids.dim() == 2 && ids.size(0) == T &&
+              ids.device() == x.device(),
+              "ids must be contiguous int32 [T, k] on x's device");
+  const int64_t k = ids.size(1);
+  TORCH_CHECK(k >= 1 && k <= 8, "moe_mlp needs 1 <= k <= 8, got ", k);
+  TORCH_CHECK(w.scalar_type() == at::kFloat && w.is_contiguous() &&
+              w.sizes() == ids.sizes() && w.device() == x.device(),
+              "w must be contiguous f32 [T, k] on x's device");
+  TORCH_CHECK(w_gate_up.device() == x.device() &&
+              w_down.device() == x.device(), "moe_mlp: device mismatch");
+  TORCH_CHECK(row_tile == 0 || row_tile == 16 || row_tile == 64,
+              "row_tile must be 0, 16 or 64");
+  TORCH_CHECK(T * k <= (1 << 24), "moe_mlp: too many rows");
+  Tensor out = at::empty({T, H}, x.options());
+  if (T == 0) return out;
+  const int R = row_tile ? int(row_tile)
+                         : rlli::moe_row_tile(int(T), int(k), int(E));
+  const int64_t n = rlli::moe_max_tiles(int(T), int(k), int(E), R);
+  const auto iopt = x.options().dtype(at::kInt);
+  Tensor sorted = at::empty({n * R}, iopt);
+  Tensor tile_expert = at::empty({n}, iopt);
+  Tensor pos = at::empty({T * k}, iopt);
+  Tensor n_live = at::empty({1}, iopt);
+  Tensor act = at::empty({n * R, I}, x.options());
+  Tensor y = at::empty({n * R, H}, x.options().dtype(at::kFloat));
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  rlli::launch_moe_mlp(bf16_ptr(x), ids.data_ptr<int32_t>(),
+                       w.data_ptr<float>(), bf16_ptr(w_gate_up),
+                       bf16_ptr(w_down), sorted.data_ptr<int32_t>(),
+                       tile_expert.data_ptr<int32_t>(),
+                       pos.data_ptr<int32_t>(), n_live.data_ptr<int32_t>(),
+                       bf16_ptr(act), y.data_ptr<float>(), bf16_ptr(out),
+                       int(T), int(k), int(E), int(H), int(I), R,
+                       current_stream(x));
+  check_launch("moe_mlp");
+  return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(rlli, m) {
@@ -1508,6 +1586,10 @@ TORCH_LIBRARY(rlli, m) {
   m.def("lora_shrink(Tensor x, Tensor A, Tensor adapter_idx) -> Tensor");
   m.def("lora_expand_add_(Tensor(a!) out, Tensor y, Tensor B, Tensor scale, "
         "int[] slices, Tensor adapter_idx) -> ()");
+  m.def("moe_route(Tensor router_logits, int k, bool renorm) -> "
+        "(Tensor, Tensor)");
+  m.def("moe_mlp(Tensor x, Tensor ids, Tensor w, Tensor w_gate_up, "
+        "Tensor w_down, int row_tile) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(rlli, CUDA, m) {
@@ -1550,4 +1632,6 @@ TORCH_LIBRARY_IMPL(rlli, CUDA, m) {
   m.impl("kv_copy_blocks_", &kv_copy_blocks_);
   m.impl("lora_shrink", &lora_shrink);
   m.impl("lora_expand_add_", &lora_expand_add_);
+  m.impl("moe_route", &moe_route);
+  m.impl("moe_mlp", &moe_mlp);
 }

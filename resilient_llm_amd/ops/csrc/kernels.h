@@ -378,4 +378,29 @@ void launch_lora_expand_add(uint16_t* out,            // [T, O] bf16, in place
                             int n_slices, const int* slice_ends,
                             hipStream_t stream);
 
+// Mixture-of-Experts MLP (moe.hip).
+//   launch_moe_route: ids[T, k] = the k largest logits of each row of
+//     logits[T, E] bf16 (descending, ties to the lower index, NaN lowest),
+//     w[T, k] = f32 softmax over all E at those ids, divided by their sum
+//     with renorm.  2 <= E <= 256, 1 <= k <= min(E, 8).
+//   launch_moe_mlp: out[t] = bf16(sum_j w[t, j] * down_e(bf16(silu(gate_e
+//     (x[t])) * up_e(x[t])))), e = ids[t, j], w_gate_up [E, 2I, H] (gate |
+//     up rows), w_down [E, H, I]; H % 64 == 0, I % 64 == 0.  Four launches
+//     (align, gate/up + SwiGLU, down, combine), no host sync, no float
+//     atomics.  R = moe_row_tile(T, k, E) (16 or 64) rows per tile; with
+//     n = moe_max_tiles(T, k, E, R) the workspaces are sorted int32 [n * R],
+//     tile_expert int32 [n], pos int32 [T * k], n_live int32 [1], act bf16
+//     [n * R, I] and y f32 [n * R, H]; none needs initialising.  An id
+//     outside [0, E) contributes nothing.
+int moe_row_tile(int T, int k, int E);
+int moe_max_tiles(int T, int k, int E, int R);
+void launch_moe_route(const uint16_t* logits, int32_t* ids, float* w, int T,
+                      int E, int k, bool renorm, hipStream_t stream);
+void launch_moe_mlp(const uint16_t* x, const int32_t* ids, const float* w,
+                    const uint16_t* w_gate_up, const uint16_t* w_down,
+                    int32_t* sorted, int32_t* tile_expert, int32_t* pos,
+                    int32_t* n_live, uint16_t* act, float* y, uint16_t* out,
+                    int T, int k, int E, int H, int I, int R,
+                    hipStream_t stream);
+
 }  // namespace rlli

@@ -689,3 +689,50 @@ def awq_repack(qweight, qzeros, scales, packed, meta, col_offset):
     lo = col_offset // 16 * G * 256
     packed[lo:lo + N * K // 8] = w4_pack(u.to(torch.int8) - 8)
     meta[col_offset:col_offset + N] = w4_zp_meta(z, s)
+
+
+# ------------------------------------------------------------------- MoE
+def moe_route(router_logits: torch.Tensor, k: int, renorm: bool = True):
+    """Softmax-top-k routing: (ids [T, k] int32, w [T, k] f32).  The k
+    largest logits of each row in descending order, ties to the lower
+    expert index: a STABLE descending sort of the logit values themselves
+    (not of the probabilities, where exp can merge two distinct logits),
+    NaN counted as the lowest value.  w = softmax over all E in float64 at
+    the chosen ids, divided by their sum (added in slot order) with
+    ``renorm``, then rounded to f32."""
+    lg = router_logits.double()
+    keys = torch.where(torch.isnan(lg), torch.full_like(lg, float("-inf")), lg)
+    ids = torch.sort(keys, dim=-1, descending=True, stable=True)[1][:, :k]
+    p = torch.softmax(lg, dim=-1).gather(1, ids)
+    if renorm:
+        p = p / torch.cumsum(p, dim=-1)[:, -1:]
+    return ids.to(torch.int32), p.float()
+
+
+def moe_mlp(x: torch.Tensor, ids: torch.Tensor, w: torch.Tensor,
+            w_gate_up: torch.Tensor, w_down: torch.Tensor,
+            exact: bool = False) -> torch.Tensor:
+    """out[t] = sum_j w[t, j] * Wd[e] · (silu(Wg[e] · x[t]) * (Wu[e] ·
+    x[t])), e = ids[t, j], summed in slot order; w_gate_up [E, 2I, H] holds
+    gate | up rows, w_down [E, H, I].  As the kernels: f32 math, the
+    activation rounded once to x's dtype, the output once.  ``exact``: the
+    same in float64 with no rounding at all, returned as float64 (the
+    tests' reference).  Only the experts some token chose are read."""
+    ft = torch.float64 if exact else torch.float32
+    T, H = x.shape
+    I = w_down.shape[2]
+    k = ids.shape[1]
+    xf = x.to(ft)
+    y = torch.zeros(T, k, H, dtype=ft)
+    idl = ids.long()
+    for e in torch.unique(idl).tolist():
+        tok, slot = torch.nonzero(idl == e, as_tuple=True)
+        gu = xf[tok] @ w_gate_up[e].to(ft).T
+        act = torch.nn.functional.silu(gu[:, :I]) * gu[:, I:]
+        if not exact:
+            act = act.to(x.dtype).to(ft)
+        y[tok, slot] = act @ w_down[e].to(ft).T
+    out = torch.zeros(T, H, dtype=ft)
+    for j in range(k):
+        out += w[:, j:j + 1].to(ft) * y[:, j]
+    return out if exact else out.to(x.dtype)
